@@ -306,7 +306,10 @@ def launch_ranks(gpus: int, argv) -> int:
     return subprocess.call(cmd)
 
 
-def main():
+def parse_args(argv=None):
+    """The command line; returns (args, full). full: --full, or an experiment mode (runs of their own,
+    which keep the full defaults). The lines beside the headline (FULL_DEFAULTS) are off unless full,
+    or asked for by their own option."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="GPUs (= ranks, one process each). N > 1 without WORLD_SIZE: the bench starts the N ranks "
@@ -317,10 +320,20 @@ def main():
     ap.add_argument("--pairs", type=int, default=1_000_000, help="config 2: read pairs per rank per step")
     ap.add_argument("--species", type=int, default=25000)
     ap.add_argument("--mean-genome", type=int, default=75000)
-    ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="read pairs timed on the CPU oracle (0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: config 2, the CPU baselines and parity samples, "
+                         "the long-read, skewed, variant, file -> TSV, --em, cold-open and config-5 lines (each "
+                         "still sized by its own option). Without it those options default to off and the run "
+                         "sets up, warms up, times --steps steps of the headline and prints its line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step's last batch left in the context "
+                         "(per-read results and taxID:count lists of a fixed sample of its reads) as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="read pairs timed on the CPU oracle (0 = off; --full: 1M)")
     ap.add_argument("--seed", type=int, default=5)
-    ap.add_argument("--long-reads", type=int, default=125_000,
-                    help="config 4: ONT-style reads (N50 ~10 kb) per rank for the long-read line (1M / 8; 0 = off)")
+    ap.add_argument("--long-reads", type=int, default=None,
+                    help="config 4: ONT-style reads (N50 ~10 kb) per rank for the long-read line (0 = off; --full: "
+                         "125k = 1M / 8)")
     ap.add_argument("--long-batch", type=int, default=62_500,
                     help="long reads per mtb_classify_batch (62.5k: 2 batches per 125k-read shard; 25k: 494.6k vs 527.8k "
                          "reads/s same box, profiles/r03/long_batch_sweep.json)")
@@ -348,23 +361,25 @@ def main():
     ap.add_argument("--gtdb-true-species", type=int, default=1000)
     ap.add_argument("--gtdb-genome", type=int, default=3_000_000)
     ap.add_argument("--gtdb-cpu-sample", type=int, default=1_000_000, help="config 3: read pairs timed on the oracle")
-    ap.add_argument("--variants", default="syncmer,related,conserved",
-                    help="extra config-3 lines, comma-separated (GTDB_VARIANTS; empty = none)")
+    ap.add_argument("--variants", default=None,
+                    help="extra config-3 lines, comma-separated (GTDB_VARIANTS; empty = none; --full: "
+                         "syncmer,related,conserved)")
     ap.add_argument("--variant-cpu-sample", type=int, default=200_000,
                     help="read pairs of each variant line timed on the oracle (parity sample)")
-    ap.add_argument("--e2e-pairs", type=int, default=10_000_000,
-                    help="config 3 file -> TSV line: read pairs written as BGZF / plain FASTQ (0 = off)")
+    ap.add_argument("--e2e-pairs", type=int, default=None,
+                    help="config 3 file -> TSV line: read pairs written as BGZF / plain FASTQ (0 = off; --full: 10M)")
     ap.add_argument("--e2e-contexts", type=int, default=2,
                     help="contexts on the GPU for the file -> TSV lines (mtb_clone: two batches in flight)")
     ap.add_argument("--e2e-repeat", type=int, default=3,
                     help="file -> TSV runs per format (A/B: the line reports the median, and every run)")
-    ap.add_argument("--e2e-gzip-pairs", type=int, default=10_000_000,
-                    help="config 3 file -> TSV line: read pairs written as single-member gzip FASTQ (0 = off)")
-    ap.add_argument("--em-pairs", type=int, default=10_000_000,
-                    help="config 3 --em line: read pairs classified with em and reassigned (0 = off)")
+    ap.add_argument("--e2e-gzip-pairs", type=int, default=None,
+                    help="config 3 file -> TSV line: read pairs written as single-member gzip FASTQ (0 = off; "
+                         "--full: 10M)")
+    ap.add_argument("--em-pairs", type=int, default=None,
+                    help="config 3 --em line: read pairs classified with em and reassigned (0 = off; --full: 10M)")
     ap.add_argument("--variant-only", default="", help="experiments: run this config-3 variant line alone")
-    ap.add_argument("--c5-kmers", type=float, default=35e9,
-                    help="config 5: k-mers of the range-partitioned DB (> one GPU's HBM; 0 = off)")
+    ap.add_argument("--c5-kmers", type=float, default=None,
+                    help="config 5: k-mers of the range-partitioned DB (> one GPU's HBM; 0 = off; --full: 35e9)")
     ap.add_argument("--c5-pairs", type=int, default=10_000_000, help="config 5: read pairs per step")
     ap.add_argument("--c5-parts", type=int, default=8,
                     help="config 5 on one GPU: DB parts, each timed in turn (with N >= 4 GPUs: one part per rank)")
@@ -373,21 +388,34 @@ def main():
     ap.add_argument("--ab", default="", help="experiments: 'name=K=V,K=V;name2=...' same-box A/B of the headline")
     ap.add_argument("--ab-repeat", type=int, default=2, help="--ab: rounds over the specs")
     ap.add_argument("--ab-skewed", action="store_true", help="--ab on the skewed-abundance reads (--skew-sigma)")
-    ap.add_argument("--skewed-pairs", type=int, default=10_000_000,
-                    help="config 3: read pairs of the skewed-abundance line (log-normal genome abundance; 0 = off)")
+    ap.add_argument("--skewed-pairs", type=int, default=None,
+                    help="config 3: read pairs of the skewed-abundance line (log-normal genome abundance; 0 = off; "
+                         "--full: 10M)")
     ap.add_argument("--skew-sigma", type=float, default=2.0,
                     help="skewed line: sigma of the log-normal per-genome abundance")
-    ap.add_argument("--cold-gtdb", type=int, default=1,
-                    help="config 3: open the GTDB-scale DB from host diffIdx/info/split (mtb_open_host) and time it")
+    ap.add_argument("--cold-gtdb", type=int, default=None,
+                    help="config 3: open the GTDB-scale DB from host diffIdx/info/split (mtb_open_host) and time it "
+                         "(needs the CPU oracle's DB: --cpu-sample; 0 = off; --full: 1)")
     ap.add_argument("--cold-settle-s", type=float, default=8.0,
                     help="GTDB cold open: idle seconds after freeing the resident DB (the driver's wipe of freed HBM)")
-    ap.add_argument("--cold-pairs", type=int, default=10_000_000,
-                    help="cold one-shot line: read pairs of the file classified by a freshly opened context (0 = off)")
+    ap.add_argument("--cold-pairs", type=int, default=None,
+                    help="cold one-shot line: read pairs of the file classified by a freshly opened context (0 = off; "
+                         "--full: 10M)")
     ap.add_argument("--launch-probe", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--detail", default=DEFAULT_DETAIL,
+    ap.add_argument("--detail", default=None,
                     help="side file for the full result tree (per-kernel splits, work counters, config-5 parts, "
-                         "e2e host stages); the stdout line keeps the headline and one-line summaries")
-    args = ap.parse_args()
+                         "e2e host stages); the stdout line keeps the headline and one-line summaries (default: "
+                         "none; --full: bench_out/bench_detail.json)")
+    args = ap.parse_args(argv)
+    full = args.full or args.c5_only or bool(args.ab) or bool(args.variant_only) or args.db_parts > 1
+    for k, v in FULL_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v if full else type(v)())
+    return args, full
+
+
+def main():
+    args, full = parse_args()
 
     how, world = resolve_world(args.gpus, os.environ)
     if how == "launch":
@@ -396,8 +424,8 @@ def main():
         print(json.dumps({"rank": int(os.environ.get("RANK", "0")), "world": world,
                           "local_rank": int(os.environ.get("LOCAL_RANK", "0"))}), flush=True)
         return
-    if world > 1 and args.detail == DEFAULT_DETAIL:
-        args.detail = DEFAULT_DETAIL.replace(".json", f"_n{world}.json")
+    if args.detail is None and full:
+        args.detail = DEFAULT_DETAIL if world == 1 else DEFAULT_DETAIL.replace(".json", f"_n{world}.json")
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # rehearsal of the N > 1 paths on a one-GPU box (never the measurement): MTB_BENCH_BACKEND=gloo and
@@ -433,7 +461,9 @@ def main():
         if rank == 0:
             print(json.dumps(v))
         return
-    c2 = run_config2(args, world, rank, local, dev) if not args.skip_config2 or args.db_parts > 1 else None
+    # config 2 is a line beside the headline (--full), or the headline itself without config 3
+    c2 = (run_config2(args, world, rank, local, dev)
+          if not args.skip_config2 and (full or args.gtdb_kmers <= 0) or args.db_parts > 1 else None)
     if args.db_parts > 1:
         return
     torch.cuda.empty_cache()
@@ -476,7 +506,39 @@ def main():
         dist.destroy_process_group()
 
 
-DEFAULT_DETAIL = os.path.join(ROOT, "profiles", "r06", "bench_detail.json")
+DEFAULT_DETAIL = os.path.join(ROOT, "bench_out", "bench_detail.json")  # untracked; a record to keep: --detail
+# what --full turns on: the lines beside the headline, at the sizes the committed records ran them
+FULL_DEFAULTS = {"cpu_sample": 1_000_000, "long_reads": 125_000, "variants": "syncmer,related,conserved",
+                 "e2e_pairs": 10_000_000, "e2e_gzip_pairs": 10_000_000, "em_pairs": 10_000_000, "c5_kmers": 35e9,
+                 "skewed_pairs": 10_000_000, "cold_gtdb": 1, "cold_pairs": 10_000_000}
+DUMP_READS = 1_000_000    # --dump-outputs: reads of the last batch sampled (fixed seed)
+DUMP_TAXCNT = 2_000_000   # and the taxID:count entries kept of their lists (the whole dump stays under 64 MB)
+
+
+def dump_outputs(out_dir, clf, n):
+    """--dump-outputs: what the timed path left in the context after its last step, as a caller of
+    classify_batch(fetch=False) would fetch it: the last batch's n result records (copy_results) and
+    its pooled taxID:count lists (taxcnt). A fixed, seeded sample of DUMP_READS reads (all when the
+    batch has fewer), every record field as its own float array, and the sampled reads' lists in read
+    order (the first DUMP_TAXCNT entries): 36 + 24 MB at most."""
+    res = np.zeros(n, RESULT_DTYPE)
+    clf.copy_results(res.ctypes.data, on_device=False)
+    tc = clf.taxcnt()
+    idx = np.arange(n) if n <= DUMP_READS else np.sort(np.random.default_rng(20240229).choice(n, DUMP_READS, False))
+    r = res[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "read_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "classification.npy"), r["classification"].astype(np.float64))
+    np.save(os.path.join(out_dir, "score.npy"), r["score"].astype(np.float32))
+    for k in ("hamming_dist", "query_length", "taxcnt_len", "is_classified"):
+        np.save(os.path.join(out_dir, k + ".npy"), r[k].astype(np.float32))
+    ln = r["taxcnt_len"].astype(np.int64)
+    keep = int(np.searchsorted(np.cumsum(ln), DUMP_TAXCNT, side="right"))  # whole lists only
+    ln = ln[:keep]
+    start = np.repeat(r["taxcnt_offset"][:keep].astype(np.int64) - (np.cumsum(ln) - ln), ln)
+    lists = tc[start + np.arange(int(ln.sum()))]
+    np.save(os.path.join(out_dir, "taxcnt_taxid.npy"), lists["tax_id"].astype(np.float64))
+    np.save(os.path.join(out_dir, "taxcnt_count.npy"), lists["count"].astype(np.float32))
 LINE_CAP = 8000  # the driver keeps only the tail of stdout (~15.5 KB): the one JSON line stays well under it
 
 
@@ -661,6 +723,8 @@ def run_config2(args, world, rank, local, dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs and args.gtdb_kmers <= 0 and args.steps + args.warmup > 0:
+        dump_outputs(args.dump_outputs, clf, n)  # config 2 as the headline
     kern, stage = tally.kern_avg(), tally.stage_avg()
     Qref, M = clf.last_counts()  # Qref: the reference's "Query k-mer number" (all non-blank windows)
     work = clf.stats()
@@ -1151,6 +1215,9 @@ def run_gtdb(args, world, rank, local, dev, variant=None):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs and not variant and args.steps + args.warmup > 0:
+        a, b = spans[::1 + len(peers)][-1]  # the last step's last batch (of this context)
+        dump_outputs(args.dump_outputs, clf, b - a)
     kern, stage = tally.kern_avg(), tally.stage_avg()
     Qb, Mb = tally.avg("q"), tally.avg("m")  # per 1M-pair batch
     work = clf.stats()
@@ -1161,7 +1228,7 @@ def run_gtdb(args, world, rank, local, dev, variant=None):
     names = kernel_names(work)
     roofline, rand_roof = tally.rooflines(names, rdb.n, load_traffic(variant or "gtdb", rdb.n, B), mates=2)
     value = world * N * args.steps / elapsed
-    log(rank, f"[bench] {tag}: {value / 1e6:.2f}M reads/s, {elapsed / args.steps * 1e3:.1f} ms/step, "
+    log(rank, f"[bench] {tag}: {value / 1e6:.2f}M reads/s, {elapsed / max(1, args.steps) * 1e3:.1f} ms/step, "
               f"kernels {dict(zip(names, np.round(kern, 2)))}")
     # whole pipeline against HBM: reads + query k-mers written and read (2 x 16 B) +
     # the DB bytes the join asks for (28 B per query: two run-index entries, two records) + matches
@@ -1257,7 +1324,7 @@ def run_gtdb(args, world, rank, local, dev, variant=None):
     if odb is not None:
         odb.close()
     out = {
-        "value": round(value, 1), "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "value": round(value, 1), "ms_per_step": round(elapsed / max(1, args.steps) * 1e3, 3),
         "config": {"workload": config3_label(N, L, db_n, args.gtdb_species, B, tag),
                    "read_pairs_per_gpu": N, "batch_pairs": B, "read_len": L, "db_kmers": db_n,
                    "db_true_signal_kmers": db_n_true, "db_resident_bytes": db_n * 12,

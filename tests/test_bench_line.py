@@ -188,3 +188,90 @@ def test_random_roofline_fracs_at_most_one():
             assert 0.6 < rr["match_join"]["frac"] < 0.8 and rr["filter"]["frac"] > 0.85
     assert seen >= 10
     assert b.random_roofline([1.0] * 7, b.KERNELS_SORT, (None, None)) is None  # no PMC pass: no entry
+
+
+# ---- plain run vs --full; --dump-outputs ----
+def test_plain_run_is_lean_and_full_keeps_the_lines():
+    """`bench.py --gpus 1 --steps N --warmup W` runs the headline only: every line beside it
+    (FULL_DEFAULTS) is off and no detail file is named; --full turns them on at the sizes the committed
+    records ran them, an option of a line still sizes it either way, and the experiment modes keep the
+    full defaults."""
+    b = _bench()
+    args, full = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not full and args.steps == 7 and args.warmup == 2 and args.detail is None
+    for k, v in b.FULL_DEFAULTS.items():
+        assert getattr(args, k) == type(v)() and not getattr(args, k), k
+    args, full = b.parse_args(["--full", "--em-pairs", "0"])
+    assert full and args.em_pairs == 0
+    for k, v in b.FULL_DEFAULTS.items():
+        if k != "em_pairs":
+            assert getattr(args, k) == v, k
+    args, full = b.parse_args(["--long-reads", "1000"])
+    assert not full and args.long_reads == 1000 and args.cpu_sample == 0
+    for mode in (["--variant-only", "related"], ["--c5-only"], ["--ab", "a=X=1"], ["--db-parts", "4"]):
+        args, full = b.parse_args(mode)
+        assert full and args.cpu_sample == b.FULL_DEFAULTS["cpu_sample"], mode
+
+
+class _FakeContext:
+    """Stands in for Classifier in bench.dump_outputs: one batch's records and pooled lists."""
+
+    def __init__(self, res, tc):
+        self.res, self.tc = res, tc
+
+    def copy_results(self, dst_ptr, on_device=True):
+        import ctypes
+        assert not on_device
+        ctypes.memmove(dst_ptr, self.res.ctypes.data, self.res.nbytes)
+
+    def taxcnt(self):
+        return self.tc.copy()
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 arrays, the sampled reads' fields and their taxID:count lists
+    in read order, the same sample on every call, and under 64 MB at the caps."""
+    import numpy as np
+
+    b = _bench()
+    rng = np.random.default_rng(3)
+    n = 5000
+    res = np.zeros(n, b.RESULT_DTYPE)
+    res["taxcnt_len"] = rng.integers(0, 6, n)
+    res["taxcnt_offset"] = np.cumsum(res["taxcnt_len"]) - res["taxcnt_len"]
+    res["classification"] = rng.integers(0, 1 << 30, n)
+    res["score"] = rng.random(n, dtype=np.float32)
+    res["is_classified"] = res["taxcnt_len"] > 0
+    res["query_length"] = 300
+    tc = np.zeros(int(res["taxcnt_len"].sum()), np.dtype([("tax_id", "<i4"), ("count", "<u4")]))
+    tc["tax_id"] = rng.integers(1, 1 << 30, len(tc))
+    tc["count"] = rng.integers(1, 50, len(tc))
+    clf = _FakeContext(res, tc)
+
+    def load(d):
+        return {p.stem: np.load(p) for p in sorted(d.iterdir())}
+
+    b.dump_outputs(str(tmp_path / "all"), clf, n)  # fewer reads than the cap: all of them
+    got = load(tmp_path / "all")
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert np.array_equal(got["read_index"], np.arange(n))
+    assert np.array_equal(got["classification"], res["classification"])  # exact in float64
+    assert np.array_equal(got["score"], res["score"])
+    assert np.array_equal(got["taxcnt_taxid"], tc["tax_id"]) and np.array_equal(got["taxcnt_count"], tc["count"])
+
+    monkeypatch.setattr(b, "DUMP_READS", 1000)
+    monkeypatch.setattr(b, "DUMP_TAXCNT", 600)
+    b.dump_outputs(str(tmp_path / "s1"), clf, n)
+    b.dump_outputs(str(tmp_path / "s2"), clf, n)
+    s1, s2 = load(tmp_path / "s1"), load(tmp_path / "s2")
+    assert all(np.array_equal(s1[k], s2[k]) for k in s1)
+    idx = s1["read_index"].astype(np.int64)
+    assert len(idx) == 1000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(s1["taxcnt_len"], res["taxcnt_len"][idx])
+    want = np.concatenate([tc[int(r["taxcnt_offset"]):int(r["taxcnt_offset"]) + int(r["taxcnt_len"])]
+                           for r in res[idx]])
+    k = len(s1["taxcnt_taxid"])
+    assert 600 - 5 < k <= 600  # whole lists only
+    assert np.array_equal(s1["taxcnt_taxid"], want["tax_id"][:k]) and np.array_equal(s1["taxcnt_count"], want["count"][:k])
+    # at the real caps: 8 + 5 x 4 B per read + 8 B index, 12 B per list entry
+    assert _bench().DUMP_READS * 36 + _bench().DUMP_TAXCNT * 12 <= 64 * 2 ** 20

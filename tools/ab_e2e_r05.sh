@@ -5,7 +5,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05/e2e_ab
 mkdir -p $O
-B="python -u bench.py --skip-config2 --steps 1 --warmup 0 --variants= --em-pairs 0 --c5-kmers 0 --long-reads 0 --cpu-sample 0 --gtdb-cpu-sample 0 --cold-gtdb 0 --skewed-pairs 0 --cold-pairs 0 --e2e-gzip-pairs 0 --e2e-repeat 3"
+B="python -u bench.py --full --skip-config2 --steps 1 --warmup 0 --variants= --em-pairs 0 --c5-kmers 0 --long-reads 0 --cpu-sample 0 --gtdb-cpu-sample 0 --cold-gtdb 0 --skewed-pairs 0 --cold-pairs 0 --e2e-gzip-pairs 0 --e2e-repeat 3"
 for k in 1 2; do
   for spec in ${VARIANTS:-noprefault:MTB_PREFAULT=0 prefault:MTB_PREFAULT=1}; do
     name=${spec%%:*}

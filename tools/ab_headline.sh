@@ -9,7 +9,7 @@ Q="--skip-config2 --long-reads 0 --variants= --cold-pairs 0 --cpu-sample 0 --e2e
 for i in $(seq 1 ${AB_RUNS:-2}); do
   for spec in "$@"; do
     name=${spec%%=*}; envs=${spec#*=}
-    env ${envs//,/ } timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 $Q --detail $O/${name}_$i.detail.json \
+    env ${envs//,/ } timeout -k 10 300 python3 bench.py --full --steps 3 --warmup 1 $Q --detail $O/${name}_$i.detail.json \
         > $O/${name}_$i.json 2> $O/${name}_$i.err
     python3 -c "import json; d=json.load(open('$O/${name}_$i.json')); print('$name', $i, d['value'], d['kernel_ms'])"
   done

@@ -11,9 +11,9 @@ O=gpurun_out/r06/uniform
 mkdir -p $O
 GB=3333334
 Q="--skewed-pairs 0 --cold-gtdb 0 --cpu-sample 0 --e2e-pairs 0 --e2e-gzip-pairs 0 --em-pairs 0 --c5-kmers 0"
-timeout -k 10 420 python3 bench.py --skip-config2 --long-reads 0 --variants= --cold-pairs 0 $Q --steps 3 --ab-repeat 3 \
+timeout -k 10 420 python3 bench.py --full --skip-config2 --long-reads 0 --variants= --cold-pairs 0 $Q --steps 3 --ab-repeat 3 \
     --ab 'round5=MTB_UNIFORM_UNITS=0;uniform=MTB_UNIFORM_UNITS=1' > $O/ab.json 2> $O/ab.log
-CMD="bench.py --skip-config2 --steps 1 --warmup 1 --long-reads 0 --variants= --gtdb-pairs $GB --gtdb-batch $GB --cold-pairs 0 $Q"
+CMD="bench.py --full --skip-config2 --steps 1 --warmup 1 --long-reads 0 --variants= --gtdb-pairs $GB --gtdb-batch $GB --cold-pairs 0 $Q"
 for U in 0 1; do
     mkdir -p $O/u$U
     MTB_UNIFORM_UNITS=$U timeout -s KILL 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $O/u$U/fetch -o run -- python3 $CMD > /dev/null 2> $O/u$U/fetch.log

@@ -15,9 +15,9 @@ O=gpurun_out/r03/prof
 mkdir -p $O
 Q="--cpu-sample 0 --e2e-pairs 0 --e2e-gzip-pairs 0 --em-pairs 0 --c5-kmers 0"
 declare -A CMD STEP BATCH
-CMD[gtdb]="bench.py --skip-config2 --steps 1 --warmup 1 --long-reads 0 --variants= --gtdb-pairs 2000000 --gtdb-batch 2000000 $Q"
+CMD[gtdb]="bench.py --full --skip-config2 --steps 1 --warmup 1 --long-reads 0 --variants= --gtdb-pairs 2000000 --gtdb-batch 2000000 $Q"
 STEP[gtdb]=1; BATCH[gtdb]=2000000
-CMD[long]="bench.py --skip-config2 --steps 1 --warmup 0 --gtdb-pairs 2000 --gtdb-batch 1000 --variants= --long-reads 62500 --long-batch 62500 $Q"
+CMD[long]="bench.py --full --skip-config2 --steps 1 --warmup 0 --gtdb-pairs 2000 --gtdb-batch 1000 --variants= --long-reads 62500 --long-batch 62500 $Q"
 STEP[long]=3; BATCH[long]=62500
 CMD[related]="bench.py --variant-only related --steps 1 --warmup 1 --gtdb-pairs 1000000 $Q"
 STEP[related]=1; BATCH[related]=1000000
@@ -25,7 +25,7 @@ CMD[syncmer]="bench.py --variant-only syncmer --steps 1 --warmup 1 --gtdb-pairs 
 STEP[syncmer]=1; BATCH[syncmer]=1000000
 CMD[conserved]="bench.py --variant-only conserved --steps 1 --warmup 1 --gtdb-pairs 1000000 $Q"
 STEP[conserved]=1; BATCH[conserved]=1000000
-CMD[config2]="bench.py --gtdb-kmers 0 --steps 1 --warmup 1 --long-reads 0 $Q"
+CMD[config2]="bench.py --full --gtdb-kmers 0 --steps 1 --warmup 1 --long-reads 0 $Q"
 STEP[config2]=1; BATCH[config2]=1000000
 W="${@:-gtdb long related syncmer conserved config2}"
 for w in $W; do

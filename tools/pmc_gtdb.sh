@@ -6,7 +6,7 @@
 set -e
 mkdir -p gpurun_out/pmc_gtdb
 export TMPDIR=/tmp
-B="python bench.py --skip-config2 --steps 1 --warmup 0 --cpu-sample 0 --long-reads 0 --gtdb-pairs 1000000"
+B="python bench.py --full --skip-config2 --steps 1 --warmup 0 --cpu-sample 0 --long-reads 0 --gtdb-pairs 1000000"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d gpurun_out/pmc_gtdb/trace -o run -- $B > gpurun_out/pmc_gtdb/trace.log 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d gpurun_out/pmc_gtdb/fetch -o run -- $B > gpurun_out/pmc_gtdb/fetch.log 2>&1
 python tools/pmc_filter.py gpurun_out/pmc_gtdb/fetch

@@ -3,7 +3,7 @@
 set -e
 mkdir -p gpurun_out/pmc_gtdb
 export TMPDIR=/tmp
-B="python bench.py --skip-config2 --steps 1 --warmup 0 --cpu-sample 0 --gtdb-pairs 1000000"
+B="python bench.py --full --skip-config2 --steps 1 --warmup 0 --cpu-sample 0 --gtdb-pairs 1000000"
 pass() {
     local name=$1; shift
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" -f csv -d gpurun_out/pmc_gtdb/$name -o run -- $B > gpurun_out/pmc_gtdb/$name.log 2>&1

@@ -4,7 +4,7 @@
 set -e
 mkdir -p gpurun_out/pmc
 export TMPDIR=/tmp
-B="python bench.py --steps 1 --warmup 0 --cpu-sample 0"
+B="python bench.py --full --steps 1 --warmup 0 --cpu-sample 0"
 pass() {
     local name=$1; shift
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" -f csv -d gpurun_out/pmc/$name -o run -- $B > gpurun_out/pmc/$name.log 2>&1

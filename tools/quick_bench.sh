@@ -1,3 +1,5 @@
 # Config-3 kernel timing without the CPU baseline (experiments): short-read line + long-read line.
 cd $GRAFT_REPO_ROOT
-timeout -k 10 700 python -u bench.py --skip-config2 --cpu-sample 0 --steps 3 --warmup 1 "$@" > gpurun_out/qb.json 2> gpurun_out/qb.log
+O=${OUT:-bench_out}
+mkdir -p $O
+timeout -k 10 700 python -u bench.py --full --skip-config2 --cpu-sample 0 --steps 3 --warmup 1 "$@" > $O/qb.json 2> $O/qb.log

@@ -8,7 +8,7 @@ for j in ${JOINS:-default sweep sweepnf}; do
   for b in ${BATCHES:-2000000 3000000}; do
     tag=${j}_${b}
     MTB_JOIN=$([ $j = default ] && echo "" || echo sweep) MTB_FILTER=$([ $j = sweepnf ] && echo 0 || echo 1) \
-      timeout -k 10 300 python -u bench.py $common --variants "" \
+      timeout -k 10 300 python -u bench.py --full $common --variants "" \
       --gtdb-batch $b --detail gpurun_out/sw_${tag}_detail.json > gpurun_out/sw_${tag}.json 2> gpurun_out/sw_${tag}.log || exit $?
   done
 done

@@ -8,7 +8,7 @@ O=gpurun_out/r05/sq
 mkdir -p $O
 GB=3333334
 Q="--skewed-pairs 0 --cold-gtdb 0 --cpu-sample 0 --e2e-pairs 0 --e2e-gzip-pairs 0 --em-pairs 0 --c5-kmers 0"
-CMD="bench.py --skip-config2 --steps 1 --warmup 1 --long-reads 0 --variants= --gtdb-pairs $GB --gtdb-batch $GB --cold-pairs 0 $Q"
+CMD="bench.py --full --skip-config2 --steps 1 --warmup 1 --long-reads 0 --variants= --gtdb-pairs $GB --gtdb-batch $GB --cold-pairs 0 $Q"
 timeout -s KILL 300 rocprofv3 --kernel-trace --kernel-include-regex "k_segsort_regs|k_match_paths|k_choose_taxon_group|k_match<|k_radix_scatter|k_pack_live" \
   --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS \
   -f csv -d $O/p1 -o run -- python3 $CMD > /dev/null 2> $O/p1.log
