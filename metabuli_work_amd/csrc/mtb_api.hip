@@ -197,6 +197,7 @@ struct mtb_ctx {
     uint32_t longCap = 0;
     DevBuf chunkIn, chunkCnt, chunkSrcOff;  // mtb_assign_chunks staging
     DevBuf liveCnt, liveOff;                // K5 pruning: live matches per read, their offsets
+    DevBuf runFlag, runCnt, runScan;         // K6 run index: flag byte per live match; per-read group | run counts, their scans
     DevBuf segLen;                          // K5: survivors of the thinned big segments (k_thin_big)
     DevBuf sizeLists;                       // K5: reads of each size class above 128 matches (k_size_lists)
     DevBuf digA, digB;                      // K2 digit side arrays (1 B per kept query k-mer, ping-pong)
@@ -222,7 +223,7 @@ struct mtb_ctx {
     std::vector<uint32_t> spKmers;
     std::string dbDir;
     DevBuf local, paths, comb, conn, spScore, spKeep,
-        gFlag, sFlag, pathCnt, gScan, sScan, gStart, sStart, clade, tcPool, tcLen, tcOff, tcOut, results;
+        pathCnt, gStart, sStart, runGroup, clade, tcPool, tcLen, tcOff, tcOut, results;
     // last batch
     uint32_t nReads = 0;
     uint64_t Q = 0, M = 0, nTaxcnt = 0;
@@ -726,8 +727,8 @@ int mtb_clone(const mtb_ctx* src, mtb_ctx** out) {
     X(errFlag) X(ordKA) X(ordVA) X(ordKB) X(ordVB) X(matchWin) X(unitRead) X(unitInfo) X(waveList) X(waveCount) \
     X(devStats) X(mStage) X(mRank) X(mDirect) X(ovFlag) X(mTotal) X(qFrom) X(probeStats) X(longList) X(longCnt) \
     X(qStart) X(chunkIn) X(chunkCnt) X(chunkSrcOff) X(liveCnt) X(liveOff) X(segLen) X(sizeLists) X(digA) \
-    X(digB) X(binCnt) X(binTab) X(local) X(paths) X(comb) X(conn) X(spScore) X(spKeep) X(gFlag) X(sFlag) \
-    X(pathCnt) X(gScan) X(sScan) X(gStart) X(sStart) X(clade) X(tcPool) X(tcLen) X(tcOff) X(tcOut) X(results) \
+    X(digB) X(binCnt) X(binTab) X(local) X(paths) X(comb) X(conn) X(spScore) X(spKeep) X(runFlag) X(runCnt) \
+    X(runScan) X(pathCnt) X(gStart) X(sStart) X(runGroup) X(clade) X(tcPool) X(tcLen) X(tcOff) X(tcOut) X(results) \
     X(emMap) X(emCnt) X(emScratch) X(emPacked) X(emCnt32) X(emOff) X(maskOut1) X(maskOut2) X(maskProb) \
     X(maskScale) X(readLens) X(readCnt64)
 static std::vector<DevBuf*> batch_bufs(mtb_ctx* c) {
@@ -884,15 +885,27 @@ static int assign_stage(mtb_ctx* c, uint32_t n, bool keep) {
     const mtb_match* kIn = c->matchesSorted.as<mtb_match>();
     const uint64_t* kOff = c->mOff.as<uint64_t>();
     uint64_t kM = M;
+    // The K6 run flags (a byte per live match) and the per-read group and run counts are written
+    // with the live pack, or by its no-copy form where nothing was pruned. They take buffers of
+    // their own: the dead buffers below still hold the pack's input.
+    HIP_TRY(c->runCnt.ensure(sizeof(uint32_t) * 2 * ((size_t)n + 1)));
+    HIP_TRY(c->runScan.ensure(sizeof(uint64_t) * 2 * ((size_t)n + 1)));
+    uint32_t* grpCnt = c->runCnt.as<uint32_t>();
+    uint32_t* runCnt = grpCnt + n + 1;
     if (prune) {
         exclusive_scan_u32(c->liveCnt.as<uint32_t>(), n, c->liveOff.as<uint64_t>(), c->scanTmp.p, s);
         HIP_TRY(hipMemcpyAsync(&kM, c->liveOff.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        launch_pack_live(c->matchesSorted.as<mtb_match>(), c->mOff.as<uint64_t>(), c->liveOff.as<uint64_t>(), n,
-                         c->matches.as<mtb_match>(), c->errFlag.as<int>(), s);  // K5's input buffer is free again
         HIP_TRY(hipStreamSynchronize(s));
         if (kM > M) { set_error("internal error: K5 kept more matches than it sorted"); return MTB_ERR_INTERNAL; }
+        HIP_TRY(c->runFlag.ensure(std::max<uint64_t>(kM, 1)));
+        launch_run_flags(c->matchesSorted.as<mtb_match>(), c->mOff.as<uint64_t>(), c->liveOff.as<uint64_t>(), n,
+                         c->matches.as<mtb_match>(), c->runFlag.as<uint8_t>(), grpCnt, runCnt, c->errFlag.as<int>(),
+                         s);  // K5's input buffer is free again
         kIn = c->matches.as<mtb_match>();
         kOff = c->liveOff.as<uint64_t>();
+    } else {
+        HIP_TRY(c->runFlag.ensure(Mc));
+        launch_run_flags(kIn, kOff, kOff, n, nullptr, c->runFlag.as<uint8_t>(), grpCnt, runCnt, c->errFlag.as<int>(), s);
     }
     c->liveM = kM;
     c->stats[11] = kM;
@@ -927,13 +940,10 @@ static int assign_stage(mtb_ctx* c, uint32_t n, bool keep) {
                    {&c->spScore, sizeof(float) * Kc, nullptr},
                    {&c->spKeep, Kc, nullptr},
                    {&c->waveList, sizeof(uint64_t) * Kc, nullptr},
-                   {&c->gFlag, sizeof(uint32_t) * (Kc + 1), nullptr},
                    {&c->pathCnt, sizeof(uint32_t) * (Kc + 1), nullptr},
-                   {&c->sFlag, std::max<uint64_t>(sizeof(uint32_t) * (Kc + 1), run_index_tmp_bytes(Kc)), nullptr},
-                   {&c->gScan, sizeof(uint64_t) * (Kc + 1), nullptr},
-                   {&c->sScan, sizeof(uint64_t) * (Kc + 1), nullptr},
                    {&c->gStart, sizeof(uint64_t) * (Kc + 1), nullptr},
                    {&c->sStart, sizeof(uint64_t) * (Kc + 1), nullptr},
+                   {&c->runGroup, sizeof(uint64_t) * (Kc + 1), nullptr},
                    {&c->clade, clade_bytes() * Kc * c->cladePerMatch, nullptr},
                    {&c->tcPool, sizeof(mtb_taxcnt) * Kc, nullptr},
                    {&c->ordKA, sizeof(uint64_t) * (Mn + 1), nullptr},
@@ -971,26 +981,28 @@ static int assign_stage(mtb_ctx* c, uint32_t n, bool keep) {
                      need[2].p,
                      (uint8_t*)need[3].p,
                      (uint32_t*)need[7].p,
-                     (uint32_t*)need[9].p,
-                     (uint32_t*)need[8].p,
+                     (uint64_t*)need[8].p,
+                     (uint64_t*)need[9].p,
                      (uint64_t*)need[10].p,
-                     (uint64_t*)need[11].p,
-                     (uint64_t*)need[12].p,
-                     (uint64_t*)need[13].p,
+                     c->runFlag.as<uint8_t>(),
+                     grpCnt,
+                     runCnt,
+                     c->runScan.as<uint64_t>(),
+                     c->runScan.as<uint64_t>() + n + 1,
                      (float*)need[4].p,
                      (uint64_t*)need[6].p,
                      c->waveCount.as<uint32_t>(),
                      (uint8_t*)need[5].p,
                      c->scanTmp.p,
+                     (uint64_t*)need[13].p,
+                     (uint64_t*)need[14].p,
+                     (uint64_t*)need[15].p,
                      (uint64_t*)need[16].p,
-                     (uint64_t*)need[17].p,
-                     (uint64_t*)need[18].p,
-                     (uint64_t*)need[19].p,
                      c->radixCounts.as<uint32_t>(),
                      c->radixOffs.as<uint64_t>(),
-                     need[14].p,
+                     need[11].p,
                      c->cladePerMatch};
-    mtb_taxcnt* tcPool = (mtb_taxcnt*)need[15].p;
+    mtb_taxcnt* tcPool = (mtb_taxcnt*)need[12].p;
     c->stats[3] = M;
     c->stats[4] = maxSeg;
     launch_assign(kIn, kOff, c->qlen.as<uint32_t>(), n, kM, a, t, sc, tcPool,

@@ -1693,28 +1693,66 @@ hipError_t launch_segsort(const mtb_match* in, const uint64_t* mOff, uint32_t nR
                         lists);
 }
 
-// Live matches (front-packed in each sorted segment) into one dense array: a wave per read.
-__global__ void __launch_bounds__(256) k_pack_live(const mtb_match* __restrict__ in, const uint64_t* __restrict__ mOff,
+// Live matches (front-packed in each sorted segment) into one dense array, a wave per read and a
+// lane per match, with the K6 run flags on the way: the match is in registers, its predecessor one
+// lane below (read directly where a 64-match round begins), so the flag byte (bit 0: a (read,
+// species, frame) group starts, bit 1: a (read, species) run) costs no second pass over the
+// matches. A read's first match starts both. The read's group and run counts come from the ballots.
+// kCopy false (no pruning ran: kept stages, general paths): in is dense at liveOff already.
+template <bool kCopy>
+__global__ void __launch_bounds__(256) k_run_flags(const mtb_match* __restrict__ in, const uint64_t* __restrict__ mOff,
                                                    const uint64_t* __restrict__ liveOff, uint32_t nReads,
-                                                   mtb_match* __restrict__ out, int* __restrict__ err) {
+                                                   mtb_match* __restrict__ out, uint8_t* __restrict__ flags,
+                                                   uint32_t* __restrict__ grpCnt, uint32_t* __restrict__ runCnt,
+                                                   int* __restrict__ err) {
     const uint32_t r = blockIdx.x * 4 + threadIdx.x / 64;
     const uint32_t lane = threadIdx.x & 63;
     if (r >= nReads) return;
-    const uint64_t live = liveOff[r + 1] - liveOff[r];
+    const uint64_t lo = liveOff[r];
+    const uint64_t live = liveOff[r + 1] - lo;
     // a live count above the segment, or live offsets past the matches, would be a K5 bug: never
-    // copy out of bounds
-    if (live > mOff[r + 1] - mOff[r] || liveOff[r + 1] > mOff[nReads]) {
-        if (lane == 0) atomicExch(err, kErrLiveCount);
+    // copy out of bounds (the zero counts keep k_run_starts off the read's unwritten flags)
+    if (kCopy && (live > mOff[r + 1] - mOff[r] || liveOff[r + 1] > mOff[nReads])) {
+        if (lane == 0) {
+            atomicExch(err, kErrLiveCount);
+            grpCnt[r] = 0;
+            runCnt[r] = 0;
+        }
         return;
     }
-    const uint64_t* src = reinterpret_cast<const uint64_t*>(in + mOff[r]);
-    uint64_t* dst = reinterpret_cast<uint64_t*>(out + liveOff[r]);
-    for (uint64_t w = lane; w < live * 3; w += 64) dst[w] = src[w];
+    const mtb_match* src = in + (kCopy ? mOff[r] : lo);
+    uint32_t ng = 0, ns = 0;
+    for (uint64_t e0 = 0; e0 < live; e0 += 64) {
+        const uint64_t e = e0 + lane;
+        const bool on = e < live;
+        mtb_match m = {};
+        if (on) m = src[e];
+        const uint32_t sp = m.species_id, fr = info_frame(m.qinfo);
+        uint32_t psp = __shfl_up(sp, 1, 64), pfr = __shfl_up(fr, 1, 64);
+        if (lane == 0 && e0 > 0) {
+            psp = src[e0 - 1].species_id;
+            pfr = info_frame(src[e0 - 1].qinfo);
+        }
+        const bool newSp = on && (e == 0 || psp != sp);
+        const bool newG = on && (newSp || pfr != fr);
+        if (on) {
+            if (kCopy) out[lo + e] = m;
+            flags[lo + e] = (uint8_t)((uint32_t)newG | (uint32_t)newSp << 1);
+        }
+        ng += (uint32_t)__popcll(__ballot(newG));
+        ns += (uint32_t)__popcll(__ballot(newSp));
+    }
+    if (lane == 0) {
+        grpCnt[r] = ng;
+        runCnt[r] = ns;
+    }
 }
 
-void launch_pack_live(const mtb_match* in, const uint64_t* mOff, const uint64_t* liveOff, uint32_t nReads,
-                      mtb_match* out, int* err, hipStream_t s) {
-    if (nReads) k_pack_live<<<(nReads + 3) / 4, 256, 0, s>>>(in, mOff, liveOff, nReads, out, err);
+void launch_run_flags(const mtb_match* in, const uint64_t* mOff, const uint64_t* liveOff, uint32_t nReads,
+                      mtb_match* out, uint8_t* flags, uint32_t* grpCnt, uint32_t* runCnt, int* err, hipStream_t s) {
+    if (!nReads) return;
+    if (out) k_run_flags<true><<<(nReads + 3) / 4, 256, 0, s>>>(in, mOff, liveOff, nReads, out, flags, grpCnt, runCnt, err);
+    else k_run_flags<false><<<(nReads + 3) / 4, 256, 0, s>>>(in, mOff, liveOff, nReads, out, flags, grpCnt, runCnt, err);
 }
 
 __global__ void __launch_bounds__(256) k_max_seg(const uint64_t* __restrict__ off, uint32_t n, uint32_t* __restrict__ out) {
@@ -1784,7 +1822,7 @@ struct Clade {
 // match array instead of 64 unrelated per-read segments.
 // ------------------------------------------------------------------------------------------------
 
-// Run boundaries (group and species-run starts, their exclusive counts): launch_run_index,
+// Run boundaries (group and species-run starts, the per-read offsets): launch_run_flags / launch_run_starts,
 // mtb_kernels.hip.
 
 // Work list for k_match_paths: the groups that can emit a path (>= prune_min_matches matches: a
@@ -1816,12 +1854,65 @@ constexpr uint64_t kBigGroup = 256;  // groups of at least this many matches: k_
 
 // The fields getMatchPaths reads of match k: from the match array, or from a wave's LDS copy of
 // its groups' span (k_match_paths: one coalesced load of the span instead of per-lane record loads).
+// The register DP walks a group strictly forward, so it reads through a cursor (init, then advance
+// after every step to k + 1; the accessors read match k): from the match array the cursor keeps the
+// records of matches k .. k + kAhead in registers, each as pos, dna | hamming << 24 and
+// rightEndHamming, and advance issues the loads of match k + 1 + kAhead, so a lane's walk waits for
+// a record fetched kAhead steps ago instead of one memory round trip per match. No load goes at
+// or past the group's end: the index is clamped to the last match (the batch's last group ends where
+// the array ends). The serial DP re-reads the current position group, so it keeps indexed reads.
+constexpr int kAhead = 2;
+template <typename R>
+struct IndexCursor {  // indexed reads as they are (LDS; MTB_K6_LOOKAHEAD=0)
+    R r;
+    __device__ __forceinline__ void init(uint64_t, uint64_t) {}
+    __device__ __forceinline__ void advance(uint64_t) {}
+    __device__ __forceinline__ uint32_t pos(uint64_t k) const { return r.pos(k); }
+    __device__ __forceinline__ uint32_t dna(uint64_t k) const { return r.dna(k); }
+    __device__ __forceinline__ uint32_t reh(uint64_t k) const { return r.reh(k); }
+    __device__ __forceinline__ uint32_t ham(uint64_t k) const { return r.ham(k); }
+};
 struct GlobalRecs {
     const mtb_match* __restrict__ M;
     __device__ __forceinline__ uint32_t pos(uint64_t k) const { return info_pos(M[k].qinfo); }
     __device__ __forceinline__ uint32_t dna(uint64_t k) const { return M[k].dna_encoding; }
     __device__ __forceinline__ uint32_t reh(uint64_t k) const { return M[k].right_end_hamming; }
     __device__ __forceinline__ uint32_t ham(uint64_t k) const { return M[k].hamming; }
+    using Cursor = IndexCursor<GlobalRecs>;
+    __device__ __forceinline__ Cursor cursor() const { return Cursor{*this}; }
+};
+struct GlobalAhead : GlobalRecs {
+    struct Cursor {
+        const mtb_match* __restrict__ M;
+        uint64_t last;
+        uint32_t p[kAhead + 1], dh[kAhead + 1], rh[kAhead + 1];
+        __device__ __forceinline__ void fetch(uint32_t& fp, uint32_t& fdh, uint32_t& frh, uint64_t i) const {
+            const uint32_t* w = reinterpret_cast<const uint32_t*>(M + min(i, last));
+            fp = w[0];                                               // info_pos(qinfo)
+            const uint2 t = *reinterpret_cast<const uint2*>(w + 4);  // dna_encoding; reh | hamming << 16
+            fdh = (t.x & 0xFFFFFFu) | (t.y & 0xFF0000u) << 8;
+            frh = t.y & 0xFFFFu;
+        }
+        __device__ __forceinline__ void init(uint64_t start, uint64_t end) {
+            last = end - 1;
+#pragma unroll
+            for (int j = 0; j <= kAhead; j++) fetch(p[j], dh[j], rh[j], start + j);
+        }
+        __device__ __forceinline__ void advance(uint64_t k) {  // k: the match the cursor moves to
+#pragma unroll
+            for (int j = 0; j < kAhead; j++) {
+                p[j] = p[j + 1];
+                dh[j] = dh[j + 1];
+                rh[j] = rh[j + 1];
+            }
+            fetch(p[kAhead], dh[kAhead], rh[kAhead], k + kAhead);
+        }
+        __device__ __forceinline__ uint32_t pos(uint64_t) const { return p[0]; }
+        __device__ __forceinline__ uint32_t dna(uint64_t) const { return dh[0] & 0xFFFFFFu; }
+        __device__ __forceinline__ uint32_t reh(uint64_t) const { return rh[0]; }
+        __device__ __forceinline__ uint32_t ham(uint64_t) const { return dh[0] >> 24; }
+    };
+    __device__ __forceinline__ Cursor cursor() const { return Cursor{M}; }
 };
 struct LdsRecs {
     const uint32_t* p;   // pos
@@ -1832,10 +1923,12 @@ struct LdsRecs {
     __device__ __forceinline__ uint32_t dna(uint64_t k) const { return dh[k - base] & 0xFFFFFFu; }
     __device__ __forceinline__ uint32_t reh(uint64_t k) const { return rh[k - base]; }
     __device__ __forceinline__ uint32_t ham(uint64_t k) const { return dh[k - base] >> 24; }
+    using Cursor = IndexCursor<LdsRecs>;
+    __device__ __forceinline__ Cursor cursor() const { return Cursor{*this}; }
 };
 
 template <typename R>
-__device__ __forceinline__ bool match_paths_regs(const R& M, uint64_t start, uint64_t end,
+__device__ __forceinline__ bool match_paths_regs(const R& recs, uint64_t start, uint64_t end,
                                                  const AssignCfg& cfg, int minDepth, bool fwd,
                                                  Path* __restrict__ P, uint64_t& nPout, bool emitLone = false) {
     Path cp[kRegPos], np[kRegPos];
@@ -1844,6 +1937,8 @@ __device__ __forceinline__ bool match_paths_regs(const R& M, uint64_t start, uin
     int nc = 0, nn = 0;
     uint64_t nP = start;
     uint64_t k = start;
+    typename R::Cursor M = recs.cursor();
+    M.init(start, end);
     uint32_t currPos = M.pos(k);
     // first position group
     while (k < end) {
@@ -1864,6 +1959,7 @@ __device__ __forceinline__ bool match_paths_regs(const R& M, uint64_t start, uin
             }
         nc++;
         k++;
+        M.advance(k);
     }
     const bool stepped = k < end;  // a next position group follows (emitLone: see match_paths_serial)
     while (k < end) {
@@ -1887,6 +1983,7 @@ __device__ __forceinline__ bool match_paths_regs(const R& M, uint64_t start, uin
                 }
             nn++;
             k++;
+            M.advance(k);
         }
         const int shift = (int)((nextPos - currPos) / 3);
         if (shift > 0 && shift <= cfg.maxCodonShift) {
@@ -2051,7 +2148,8 @@ constexpr int kPathStage = 1024;
 // kLds = false (MTB_PATHS_NOLDS=1, A/B): no stage at all — at GTDB scale a wave's span of groups
 // rarely fits one (~2,200 matches) — so neither the 10-KB stage nor the register budget holds the
 // kernel at 4 waves per SIMD (kW: the waves the registers are held to)
-template <bool kLds, int kW>
+// kLook false (MTB_K6_LOOKAHEAD=0, A/B and tests): the unstaged groups' records by indexed reads
+template <bool kLds, int kW, bool kLook>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kW))) k_match_paths(const mtb_match* __restrict__ M, const uint64_t* __restrict__ gStart,
                                                     const uint64_t* __restrict__ order, uint64_t nWork, AssignCfg cfg,
                                                     TaxView tax, Path* __restrict__ L, Path* __restrict__ P,
@@ -2082,6 +2180,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kW))) k
     }
     if (staged)
         match_paths_group(LdsRecs{sPos, sDh, sReh, spanLo}, M, g, start, end, cfg, tax, L, P, conn, pathCnt);
+    else if (kLook)
+        match_paths_group(GlobalAhead{M}, M, g, start, end, cfg, tax, L, P, conn, pathCnt);
     else
         match_paths_group(GlobalRecs{M}, M, g, start, end, cfg, tax, L, P, conn, pathCnt);
 }
@@ -2100,6 +2200,7 @@ __device__ __forceinline__ bool group_break(const mtb_match* __restrict__ M, uin
     return !(shift > 0 && shift <= maxCodonShift);
 }
 
+template <bool kLook>
 __global__ void __launch_bounds__(64) k_match_paths_wave(const mtb_match* __restrict__ M,
                                                          const uint64_t* __restrict__ gStart,
                                                          const uint64_t* __restrict__ bigList, AssignCfg cfg,
@@ -2122,7 +2223,9 @@ __global__ void __launch_bounds__(64) k_match_paths_wave(const mtb_match* __rest
     uint64_t cnt = 0;
     if (a < b) {  // the register DP when no position of the stretch holds more than kRegPos matches
         uint64_t nPr = a;
-        if (!cfg.generic && match_paths_regs(GlobalRecs{M}, a, b, cfg, minDepth, fwd, P, nPr, multi)) cnt = nPr - a;
+        const bool regs = !cfg.generic && (kLook ? match_paths_regs(GlobalAhead{M}, a, b, cfg, minDepth, fwd, P, nPr, multi)
+                                                 : match_paths_regs(GlobalRecs{M}, a, b, cfg, minDepth, fwd, P, nPr, multi));
+        if (regs) cnt = nPr - a;
         else cnt = match_paths_serial(GlobalRecs{M}, a, b, cfg, minDepth, fwd, L, P, conn, multi) - a;
     }
     // exclusive scan of the counts over the lanes
@@ -2223,7 +2326,7 @@ constexpr int kWaveCombineMin = 24;
 constexpr int kWaveCombineMax = 1024;
 
 __global__ void __launch_bounds__(256) k_combine_paths(const mtb_match* __restrict__ M, const uint64_t* __restrict__ sStart,
-                                                       uint64_t nS, const uint64_t* __restrict__ gScan,
+                                                       uint64_t nS, const uint64_t* __restrict__ runGroup,
                                                        const uint64_t* __restrict__ gStart,
                                                        const uint32_t* __restrict__ pathCnt,
                                                        const uint32_t* __restrict__ qlen, AssignCfg cfg,
@@ -2234,7 +2337,7 @@ __global__ void __launch_bounds__(256) k_combine_paths(const mtb_match* __restri
     if (s >= nS) return;
     const uint64_t ss = sStart[s], se = sStart[s + 1];
     uint64_t w = ss;
-    for (uint64_t g = gScan[ss]; gStart[g] < se; g++) {
+    for (uint64_t g = runGroup[s]; gStart[g] < se; g++) {
         const uint64_t src = gStart[g];
         const uint32_t cnt = pathCnt[g];
         if (src != w)
@@ -2415,12 +2518,12 @@ __global__ void __launch_bounds__(64) k_combine_wave(const mtb_match* __restrict
 // in order, with no per-read quotient table. taxCnt goes to tc (capacity >= nb) in std::map order
 // (ascending taxID); returns its length.
 __device__ long filter_redundant_serial(const mtb_match* __restrict__ M, uint64_t bestFirst, uint64_t bestSecond,
-                                        const uint64_t* __restrict__ gScan, const uint64_t* __restrict__ gStart,
+                                        uint64_t bestGroup, const uint64_t* __restrict__ gStart,
                                         uint32_t dnaShift, const TaxView& tax, mtb_taxcnt* __restrict__ tc) {
     uint32_t fc[6], fin[6], head[6];
     const mtb_match* B = M + bestFirst;
     int nf = 0;
-    for (uint64_t g = gScan[bestFirst]; nf < 6 && gStart[g] < bestSecond; g++) {
+    for (uint64_t g = bestGroup; nf < 6 && gStart[g] < bestSecond; g++) {
         fc[nf] = (uint32_t)(gStart[g] - bestFirst);
         fin[nf] = (uint32_t)(gStart[g + 1] - bestFirst);
         nf++;
@@ -2573,9 +2676,9 @@ __device__ __forceinline__ mtb_result empty_result(int readLength) {
 // lower-rank BFS (:252-314): one thread per read (short reads).
 __global__ void __launch_bounds__(256) k_choose_taxon(const mtb_match* __restrict__ M, const uint64_t* __restrict__ mOff,
                                                       const uint32_t* __restrict__ qlen, uint32_t nReads,
-                                                      const uint64_t* __restrict__ sScan,
+                                                      const uint64_t* __restrict__ runOff,
                                                       const uint64_t* __restrict__ sStart,
-                                                      const uint64_t* __restrict__ gScan,
+                                                      const uint64_t* __restrict__ runGroup,
                                                       const uint64_t* __restrict__ gStart,
                                                       const float* __restrict__ spScore,
                                                       const uint8_t* __restrict__ spKeep, AssignCfg cfg, TaxView tax,
@@ -2591,15 +2694,15 @@ __global__ void __launch_bounds__(256) k_choose_taxon(const mtb_match* __restric
     if (n == 0) { results[r] = res; return; }
 
     // ---- getBestSpeciesMatches tail (Taxonomer.cpp:380-408) over the read's species runs ----
-    const uint64_t s0 = sScan[base], s1 = sScan[base + n];
+    const uint64_t s0 = runOff[r], s1 = runOff[r + 1];
     long meaningful = 0;
     float bestSpScore = 0.0f;
-    uint64_t bestFirst = 0, bestSecond = 0;
+    uint64_t bestFirst = 0, bestSecond = 0, bestRun = 0;
     for (uint64_t s = s0; s < s1; s++) {
         if (!spKeep[s]) continue;
         const float score = spScore[s];
         if (score > 0.f) meaningful++;
-        if (score > bestSpScore) { bestSpScore = score; bestFirst = sStart[s]; bestSecond = sStart[s + 1]; }
+        if (score > bestSpScore) { bestSpScore = score; bestFirst = sStart[s]; bestSecond = sStart[s + 1]; bestRun = s; }
     }
 
     // ---- chooseBestTaxon (Taxonomer.cpp:130-202) ----
@@ -2639,7 +2742,7 @@ __global__ void __launch_bounds__(256) k_choose_taxon(const mtb_match* __restric
         return;
     }
     mtb_taxcnt* tc = tcP + base;  // capacity n (each quotient holds >= 1 match)
-    const long nTc = filter_redundant_serial(M, bestFirst, bestSecond, gScan, gStart, (uint32_t)cfg.dnaShift, tax, tc);
+    const long nTc = filter_redundant_serial(M, bestFirst, bestSecond, runGroup[bestRun], gStart, (uint32_t)cfg.dnaShift, tax, tc);
     classify_tail(res, tc, nTc, spTotal, bestTax, readLength, cfg, tax, cladeP + base * cladePerMatch,
                   n * (long)cladePerMatch);
     results[r] = res;
@@ -2669,9 +2772,9 @@ __device__ __forceinline__ long wave_sum_l(long x) {
 
 __global__ void __launch_bounds__(64) k_choose_taxon_wave(const mtb_match* __restrict__ M, const uint64_t* __restrict__ mOff,
                                                           const uint32_t* __restrict__ qlen, uint32_t nReads,
-                                                          const uint64_t* __restrict__ sScan,
+                                                          const uint64_t* __restrict__ runOff,
                                                           const uint64_t* __restrict__ sStart,
-                                                          const uint64_t* __restrict__ gScan,
+                                                          const uint64_t* __restrict__ runGroup,
                                                           const uint64_t* __restrict__ gStart,
                                                           const float* __restrict__ spScore,
                                                           const uint8_t* __restrict__ spKeep, AssignCfg cfg,
@@ -2696,7 +2799,7 @@ __global__ void __launch_bounds__(64) k_choose_taxon_wave(const mtb_match* __res
         if (lane == 0) results[r] = res;
         return;
     }
-    const uint64_t s0 = sScan[base], s1 = sScan[base + n];
+    const uint64_t s0 = runOff[r], s1 = runOff[r + 1];
     long meaningful = 0;
     float bestSpScore = 0.0f;
     for (uint64_t s = s0 + lane; s < s1; s += 64) {
@@ -2710,7 +2813,7 @@ __global__ void __launch_bounds__(64) k_choose_taxon_wave(const mtb_match* __res
     float spTotal = 0.0f;
     int32_t bestTax = 0;
     bool isLCA = false;
-    uint64_t bestFirst = 0, bestSecond = 0;
+    uint64_t bestFirst = 0, bestSecond = 0, bestRun = 0;
     if (meaningful > 0) {
         // the first species run reaching the maximum (the serial scan keeps the first strict max)
         for (uint64_t c = s0; c < s1; c += 64) {
@@ -2719,6 +2822,7 @@ __global__ void __launch_bounds__(64) k_choose_taxon_wave(const mtb_match* __res
             const unsigned long long m = __ballot(hit);
             if (m) {
                 const uint64_t sb = c + (uint64_t)(__ffsll((long long)m) - 1);
+                bestRun = sb;
                 bestFirst = sStart[sb];
                 bestSecond = sStart[sb + 1];
                 break;
@@ -2836,7 +2940,7 @@ __global__ void __launch_bounds__(64) k_choose_taxon_wave(const mtb_match* __res
     }
     if (lane != 0) return;
     if (nTc < 0) {
-        nTc = filter_redundant_serial(M, bestFirst, bestSecond, gScan, gStart, dnaShift, tax, tc);
+        nTc = filter_redundant_serial(M, bestFirst, bestSecond, runGroup[bestRun], gStart, dnaShift, tax, tc);
     } else {
         for (long a = 1; a < nTc; a++) {
             mtb_taxcnt v = tc[a];
@@ -2873,9 +2977,9 @@ __device__ __forceinline__ long group_sum_l(long x) {
 __global__ void __launch_bounds__(256) k_choose_taxon_group(const mtb_match* __restrict__ M,
                                                             const uint64_t* __restrict__ mOff,
                                                             const uint32_t* __restrict__ qlen, uint32_t nReads,
-                                                            const uint64_t* __restrict__ sScan,
+                                                            const uint64_t* __restrict__ runOff,
                                                             const uint64_t* __restrict__ sStart,
-                                                            const uint64_t* __restrict__ gScan,
+                                                            const uint64_t* __restrict__ runGroup,
                                                             const uint64_t* __restrict__ gStart,
                                                             const float* __restrict__ spScore,
                                                             const uint8_t* __restrict__ spKeep, AssignCfg cfg,
@@ -2898,9 +3002,9 @@ __global__ void __launch_bounds__(256) k_choose_taxon_group(const mtb_match* __r
     float spTotal = 0.0f;
     int32_t bestTax = 0;
     bool isLCA = false, filter = false;
-    uint64_t bestFirst = 0, bestSecond = 0;
+    uint64_t bestFirst = 0, bestSecond = 0, bestRun = 0;
     if (n > 0) {
-        const uint64_t s0 = sScan[base], s1 = sScan[base + n];
+        const uint64_t s0 = runOff[r], s1 = runOff[r + 1];
         long meaningful = 0;
         float bestSpScore = 0.0f;
         for (uint64_t s = s0 + gl; s < s1; s += kGroupLanes) {
@@ -2918,7 +3022,8 @@ __global__ void __launch_bounds__(256) k_choose_taxon_group(const mtb_match* __r
                 const uint32_t m = (uint32_t)(__ballot(hit) >> gLane0) & 0xFFFFu;
                 if (m) {
                     const uint64_t sb = c + (uint64_t)(__ffs((int)m) - 1);
-                    bestFirst = sStart[sb];
+                    bestRun = sb;
+                bestFirst = sStart[sb];
                     bestSecond = sStart[sb + 1];
                     break;
                 }
@@ -3046,7 +3151,7 @@ __global__ void __launch_bounds__(256) k_choose_taxon_group(const mtb_match* __r
         return;
     }
     if (nTc < 0) {
-        nTc = filter_redundant_serial(M, bestFirst, bestSecond, gScan, gStart, dnaShift, tax, tc);
+        nTc = filter_redundant_serial(M, bestFirst, bestSecond, runGroup[bestRun], gStart, dnaShift, tax, tc);
     } else {
         for (long a = 1; a < nTc; a++) {
             mtb_taxcnt v = tc[a];
@@ -3089,14 +3194,16 @@ void launch_assign(const mtb_match* matches, const uint64_t* mOff, const uint32_
     AssignCfg cfg{a.kmerFormat, a.dnaShift, a.maxCodonShift, a.denominator, a.minConsCnt, a.minConsCntEuk,
                   a.accessionLevel, a.minScore, a.minSpScore, a.tieRatio, a.generic, a.emulateAll, a.em};
     TaxView tv{t.nodeOf, t.nodeTax, t.parent, t.depth, t.flags, t.spParent, t.maxTax};
+    // the run index from the flag bytes and per-read counts launch_run_flags left: the scans of
+    // the counts place each read's groups and runs, and their last entries are the totals
+    exclusive_scan_u32(s.grpCnt, nReads, s.grpOff, s.scanTmp, st);
+    exclusive_scan_u32(s.runCnt, nReads, s.runOff, s.scanTmp, st);
     if (nM) {
-        // gFlag holds the flag bytes, sFlag the packed tile sums (run_index_tmp_bytes)
-        launch_run_index(matches, nM, reinterpret_cast<uint8_t*>(s.gFlag),
-                         reinterpret_cast<unsigned long long*>(s.sFlag), s.gScan, s.sScan, s.gStart, s.sStart, st);
+        launch_run_starts(s.runFlag, mOff, s.grpOff, s.runOff, nReads, s.gStart, s.sStart, s.runGroup, st);
         // groups and runs never outnumber matches: size the grids by nM, threads past the count exit
         uint64_t cnt[2] = {0, 0};
-        hipMemcpyAsync(&cnt[0], s.gScan + nM, sizeof(uint64_t), hipMemcpyDeviceToHost, st);
-        hipMemcpyAsync(&cnt[1], s.sScan + nM, sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(&cnt[0], s.grpOff + nReads, sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(&cnt[1], s.runOff + nReads, sizeof(uint64_t), hipMemcpyDeviceToHost, st);
         hipStreamSynchronize(st);
         hostStats[0] = cnt[0];
         hostStats[2] = cnt[1];
@@ -3115,29 +3222,37 @@ void launch_assign(const mtb_match* matches, const uint64_t* mOff, const uint32_
                 // MTB_PATHS_NOLDS=<waves> (A/B, read per batch): the unstaged form held to 5 or 6 waves
                 const char* nl = getenv("MTB_PATHS_NOLDS");
                 const int nlw = nl ? atoi(nl) : 0;
-#define MTB_PATHS(L, W)                                                                                             \
-    k_match_paths<L, W><<<(unsigned)((heavy + 63) / 64), 64, 0, st>>>(                                              \
+                // MTB_K6_LOOKAHEAD=0 (A/B and tests, read per batch): the path DP's records by indexed reads
+                const char* la = getenv("MTB_K6_LOOKAHEAD");
+                const bool look = !la || atoi(la) != 0;
+#define MTB_PATHS(L, W, A)                                                                                          \
+    k_match_paths<L, W, A><<<(unsigned)((heavy + 63) / 64), 64, 0, st>>>(                                              \
         matches, s.gStart, inB ? s.ordKB : s.ordKA, heavy, cfg, tv, (Path*)s.local, (Path*)s.paths, s.conn,         \
         s.pathCnt, waves ? s.waveList : nullptr, s.waveCount)
-                if (nlw == 6) MTB_PATHS(false, 6);
-                else if (nlw == 5) MTB_PATHS(false, 5);
-                else if (nlw == 4) MTB_PATHS(false, 4);
-                else MTB_PATHS(true, 1);
+                if (nlw == 6) MTB_PATHS(false, 6, false);
+                else if (nlw == 5) MTB_PATHS(false, 5, false);
+                else if (nlw == 4 && look) MTB_PATHS(false, 4, true);
+                else if (nlw == 4) MTB_PATHS(false, 4, false);
+                else if (look) MTB_PATHS(true, 1, true);
+                else MTB_PATHS(true, 1, false);
 #undef MTB_PATHS
                 if (waves) {
                     uint32_t nBig = 0;
                     hipMemcpyAsync(&nBig, s.waveCount, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
                     hipStreamSynchronize(st);
-                    if (nBig)
-                        k_match_paths_wave<<<nBig, 64, 0, st>>>(matches, s.gStart, s.waveList, cfg, tv, (Path*)s.local,
-                                                                (Path*)s.paths, s.conn, s.pathCnt);
+                    if (nBig && look)
+                        k_match_paths_wave<true><<<nBig, 64, 0, st>>>(matches, s.gStart, s.waveList, cfg, tv, (Path*)s.local,
+                                                                      (Path*)s.paths, s.conn, s.pathCnt);
+                    else if (nBig)
+                        k_match_paths_wave<false><<<nBig, 64, 0, st>>>(matches, s.gStart, s.waveList, cfg, tv, (Path*)s.local,
+                                                                       (Path*)s.paths, s.conn, s.pathCnt);
                 }
             }
         }
         if (cnt[1]) {
             hipMemsetAsync(s.waveCount, 0, sizeof(uint32_t), st);
             k_combine_paths<<<(unsigned)((cnt[1] + 255) / 256), 256, 0, st>>>(
-                matches, s.sStart, cnt[1], s.gScan, s.gStart, s.pathCnt, qlen, cfg, (Path*)s.paths, (Path*)s.comb,
+                matches, s.sStart, cnt[1], s.runGroup, s.gStart, s.pathCnt, qlen, cfg, (Path*)s.paths, (Path*)s.comb,
                 s.spScore, s.spKeep, s.waveList, s.waveCount);
             uint32_t nWave = 0;
             hipMemcpyAsync(&nWave, s.waveCount, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
@@ -3150,8 +3265,6 @@ void launch_assign(const mtb_match* matches, const uint64_t* mOff, const uint32_
             }
             hostStats[3] = nWave;
         }
-    } else {
-        hipMemsetAsync(s.sScan, 0, sizeof(uint64_t), st);
     }
     // a wave per read when reads carry many matches (long reads: a thread per read would leave most
     // SIMDs idle and serialise each read's best-species scan), else a 16-lane group per read (a
@@ -3161,19 +3274,19 @@ void launch_assign(const mtb_match* matches, const uint64_t* mOff, const uint32_
     // fetched per batch against a thread per read; profiles/r03/ab_k6_group.json)
     const bool group = a.waveTaxon == 2 || (a.waveTaxon < 0 && !wave && !a.generic);
     if (group) {
-        k_choose_taxon_group<<<(nReads + 15) / 16, 256, 0, st>>>(matches, mOff, qlen, nReads, s.sScan, s.sStart,
-                                                                 s.gScan, s.gStart, s.spScore, s.spKeep, cfg, tv,
+        k_choose_taxon_group<<<(nReads + 15) / 16, 256, 0, st>>>(matches, mOff, qlen, nReads, s.runOff, s.sStart,
+                                                                 s.runGroup, s.gStart, s.spScore, s.spKeep, cfg, tv,
                                                                  (Clade*)s.clade, s.cladePerMatch, tcPool, results);
     } else if (wave) {
         k_read_size_keys<<<(nReads + 255) / 256, 256, 0, st>>>(mOff, nReads, s.ordKA);
         const uint64_t* order = longest_first(nReads, 24, s, st);
-        k_choose_taxon_wave<<<nReads, 64, 0, st>>>(matches, mOff, qlen, nReads, s.sScan, s.sStart, s.gScan, s.gStart,
+        k_choose_taxon_wave<<<nReads, 64, 0, st>>>(matches, mOff, qlen, nReads, s.runOff, s.sStart, s.runGroup, s.gStart,
                                                    s.spScore, s.spKeep, cfg, tv, (Clade*)s.clade, s.cladePerMatch,
                                                    tcPool, results, order);
     } else {
         const unsigned ctT = nReads < 256u * 256u ? 64u : 256u;
-        k_choose_taxon<<<(nReads + ctT - 1) / ctT, ctT, 0, st>>>(matches, mOff, qlen, nReads, s.sScan, s.sStart,
-                                                             s.gScan, s.gStart, s.spScore, s.spKeep, cfg, tv,
+        k_choose_taxon<<<(nReads + ctT - 1) / ctT, ctT, 0, st>>>(matches, mOff, qlen, nReads, s.runOff, s.sStart,
+                                                             s.runGroup, s.gStart, s.spScore, s.spKeep, cfg, tv,
                                                              (Clade*)s.clade, s.cladePerMatch, tcPool, results);
     }
 }
@@ -3255,7 +3368,7 @@ struct EmPair {
 };
 
 __global__ void k_em_top(const mtb_match* __restrict__ M, const uint64_t* __restrict__ mOff, uint32_t n,
-                         const uint64_t* __restrict__ sScan, const uint64_t* __restrict__ sStart,
+                         const uint64_t* __restrict__ runOff, const uint64_t* __restrict__ sStart,
                          const float* __restrict__ spScore, const uint8_t* __restrict__ spKeep,
                          const mtb_result* __restrict__ results, EmPair* __restrict__ scratch,
                          EmPair* __restrict__ maps, uint8_t* __restrict__ cnt) {
@@ -3263,8 +3376,7 @@ __global__ void k_em_top(const mtb_match* __restrict__ M, const uint64_t* __rest
     if (r >= n) return;
     cnt[r] = 0;
     if (!results[r].is_classified) return;
-    const uint64_t base = mOff[r], end = mOff[r + 1];
-    const uint64_t s0 = sScan[base], s1 = sScan[end];
+    const uint64_t s0 = runOff[r], s1 = runOff[r + 1];
     EmPair* v = scratch + s0;
     long k = 0;
     for (uint64_t s = s0; s < s1; s++)  // sp2score in species order (Taxonomer.cpp:330-369)
@@ -3278,7 +3390,7 @@ __global__ void k_em_top(const mtb_match* __restrict__ M, const uint64_t* __rest
 void launch_em_top(const mtb_match* M, const uint64_t* mOff, uint32_t n, const AssignScratch& s,
                    const mtb_result* results, void* scratch, void* maps, uint8_t* cnt, hipStream_t st) {
     if (!n) return;
-    k_em_top<<<(n + 255) / 256, 256, 0, st>>>(M, mOff, n, s.sScan, s.sStart, s.spScore, s.spKeep, results,
+    k_em_top<<<(n + 255) / 256, 256, 0, st>>>(M, mOff, n, s.runOff, s.sStart, s.spScore, s.spKeep, results,
                                               (EmPair*)scratch, (EmPair*)maps, cnt);
 }
 

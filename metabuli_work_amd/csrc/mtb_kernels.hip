@@ -117,107 +117,51 @@ uint64_t scan_tmp_elems(uint64_t n) { return (n + kScanTile - 1) / kScanTile + 1
 // ------------------------------------------------------------------------------------------------
 // K6 run index over the sorted live matches (the loops of Taxonomer.cpp:316-408): a (read, species,
 // frame) group starts where the read, species or frame changes, a (read, species) run where the
-// read or species changes. Two passes over 8192-match tiles instead of flags + two device scans +
-// a start scatter: pass 1 reads the matches once, writes one flag byte per match (bit 0 group,
-// bit 1 run) and the tile's two counts packed in one u64 (groups low, runs high: both < 2^32);
-// the tile sums are scanned as packed u64; pass 2 reads the bytes (32 per thread, two 16-B loads),
-// scans them, and writes gScan/sScan (exclusive counts, u64) through LDS so the stores stay
-// coalesced, and each group's / run's first match index. gScan[nM], sScan[nM] = the totals, and
-// gStart / sStart end with nM.
+// read or species changes. k_run_flags (mtb_assign.hip: the live pack, or its no-copy form) wrote
+// one flag byte per match (bit 0 group, bit 1 run) and each read's two counts; their exclusive
+// scans are grpOff / runOff (per read). Here a wave per read turns the read's flag bytes into each
+// group's / run's first match index (gStart / sStart, closed with nM) and each run's first group
+// (runGroup). Nothing per match is written: K6 reads the index at read boundaries and run starts only.
 // ------------------------------------------------------------------------------------------------
-constexpr int kRunItems = 32;
-constexpr int kRunTile = kBlock * kRunItems;  // 8192 matches
-
-__global__ void __launch_bounds__(256) k_run_tiles(const mtb_match* __restrict__ M, uint64_t nM,
-                                                   uint8_t* __restrict__ flags, unsigned long long* __restrict__ tileSum) {
-    const uint64_t base = (uint64_t)blockIdx.x * kRunTile;
-    unsigned long long s = 0;
-#pragma unroll 8
-    for (int k = 0; k < kRunItems; k++) {
-        const uint64_t i = base + (uint64_t)k * kBlock + threadIdx.x;
-        if (i >= nM) break;
-        uint32_t g = 1, sp = 1;
-        if (i > 0) {
-            const uint64_t qa = M[i - 1].qinfo, qb = M[i].qinfo;
-            const bool newSp = info_seq(qa) != info_seq(qb) || M[i - 1].species_id != M[i].species_id;
-            sp = newSp;
-            g = newSp || info_frame(qa) != info_frame(qb);
+__global__ void __launch_bounds__(256) k_run_starts(const uint8_t* __restrict__ flags, const uint64_t* __restrict__ mOff,
+                                                    const uint64_t* __restrict__ grpOff,
+                                                    const uint64_t* __restrict__ runOff, uint32_t nReads,
+                                                    uint64_t* __restrict__ gStart, uint64_t* __restrict__ sStart,
+                                                    uint64_t* __restrict__ runGroup) {
+    const uint32_t r = blockIdx.x * 4 + threadIdx.x / 64;
+    const uint32_t lane = threadIdx.x & 63;
+    if (r >= nReads) return;
+    const uint64_t lo = mOff[r], live = mOff[r + 1] - lo;
+    const uint64_t g0 = grpOff[r], s0 = runOff[r];
+    // the counts bound every store: flag bytes that disagreed with them would be a pack bug
+    const uint64_t gN = grpOff[r + 1] - g0, sN = runOff[r + 1] - s0;
+    const unsigned long long below = (1ull << lane) - 1;
+    uint64_t jg = 0, js = 0;
+    for (uint64_t e0 = 0; e0 < live; e0 += 64) {
+        const uint64_t e = e0 + lane;
+        const uint32_t f = e < live ? flags[lo + e] : 0u;
+        const unsigned long long mg = __ballot(f & 1u), ms = __ballot(f & 2u);
+        const uint64_t g = jg + __popcll(mg & below);
+        if ((f & 1u) && g < gN) gStart[g0 + g] = lo + e;
+        if (f & 2u) {
+            const uint64_t s = js + __popcll(ms & below);
+            if (s < sN) {
+                sStart[s0 + s] = lo + e;
+                runGroup[s0 + s] = g0 + g;  // a run starts a group
+            }
         }
-        flags[i] = (uint8_t)(g | sp << 1);
-        s += (unsigned long long)g | (unsigned long long)sp << 32;
+        jg += __popcll(mg);
+        js += __popcll(ms);
     }
-    unsigned long long tot;
-    block_exclusive_scan(s, &tot);
-    if (threadIdx.x == 0) tileSum[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(256) k_run_index(const uint8_t* __restrict__ flags, uint64_t nM,
-                                                   const unsigned long long* __restrict__ tileSum,
-                                                   uint64_t* __restrict__ gScan, uint64_t* __restrict__ sScan,
-                                                   uint64_t* __restrict__ gStart, uint64_t* __restrict__ sStart) {
-    __shared__ uint32_t sIdx[kRunTile];  // tile-relative exclusive count of one kind, per match
-    __shared__ uint8_t sF[kRunTile];
-    const uint64_t base = (uint64_t)blockIdx.x * kRunTile;
-    const uint32_t nT = (uint32_t)min<uint64_t>(kRunTile, nM - base);
-    const int tid = threadIdx.x;
-    // bytes in: coalesced 16-B loads into LDS (the tile is 8192 bytes), then 32 contiguous per thread
-    if (nT == kRunTile) {
-        const uint4* src = reinterpret_cast<const uint4*>(flags + base);
-        uint4* dst = reinterpret_cast<uint4*>(sF);
-        for (int x = tid; x < kRunTile / 16; x += kBlock) dst[x] = src[x];
-    } else {
-        for (uint32_t x = tid; x < nT; x += kBlock) sF[x] = flags[base + x];
-    }
-    __syncthreads();
-    uint32_t f[kRunItems];
-    unsigned long long s = 0;
-#pragma unroll
-    for (int k = 0; k < kRunItems; k++) {
-        const uint32_t x = (uint32_t)tid * kRunItems + k;
-        f[k] = x < nT ? sF[x] : 0u;
-        s += (unsigned long long)(f[k] & 1u) | (unsigned long long)(f[k] >> 1) << 32;
-    }
-    unsigned long long tot;
-    const unsigned long long ex = block_exclusive_scan(s, &tot);
-    const unsigned long long tb = tileSum[blockIdx.x];
-    const uint64_t gBase = tb & 0xFFFFFFFFull, sBase = tb >> 32;
-#pragma unroll
-    for (int kind = 0; kind < 2; kind++) {
-        uint32_t run = kind ? (uint32_t)(ex >> 32) : (uint32_t)ex;
-#pragma unroll
-        for (int k = 0; k < kRunItems; k++) {
-            sIdx[tid * kRunItems + k] = run;
-            run += (f[k] >> kind) & 1u;
-        }
-        __syncthreads();
-        uint64_t* scan = kind ? sScan : gScan;
-        uint64_t* start = kind ? sStart : gStart;
-        const uint64_t b0 = kind ? sBase : gBase;
-        for (uint32_t x = tid; x < nT; x += kBlock) {
-            const uint64_t v = b0 + sIdx[x];
-            scan[base + x] = v;
-            if ((sF[x] >> kind) & 1u) start[v] = base + x;
-        }
-        __syncthreads();
-    }
-    if (blockIdx.x == gridDim.x - 1 && tid == 0) {
-        const unsigned long long all = tileSum[gridDim.x];
-        gScan[nM] = all & 0xFFFFFFFFull;
-        sScan[nM] = all >> 32;
-        gStart[all & 0xFFFFFFFFull] = nM;
-        sStart[all >> 32] = nM;
+    if (r == nReads - 1 && lane == 0) {
+        gStart[grpOff[nReads]] = mOff[nReads];
+        sStart[runOff[nReads]] = mOff[nReads];
     }
 }
 
-uint64_t run_index_tmp_bytes(uint64_t nM) { return 8 * ((nM + kRunTile - 1) / kRunTile + 2); }
-
-void launch_run_index(const mtb_match* M, uint64_t nM, uint8_t* flags, unsigned long long* tileSum, uint64_t* gScan,
-                      uint64_t* sScan, uint64_t* gStart, uint64_t* sStart, hipStream_t s) {
-    if (nM == 0) return;
-    const uint64_t tiles = (nM + kRunTile - 1) / kRunTile;
-    k_run_tiles<<<(unsigned)tiles, kBlock, 0, s>>>(M, nM, flags, tileSum);
-    k_scan_tile_sums<<<1, kBlock, 0, s>>>(tileSum, tiles);
-    k_run_index<<<(unsigned)tiles, kBlock, 0, s>>>(flags, nM, tileSum, gScan, sScan, gStart, sStart);
+void launch_run_starts(const uint8_t* flags, const uint64_t* mOff, const uint64_t* grpOff, const uint64_t* runOff,
+                       uint32_t nReads, uint64_t* gStart, uint64_t* sStart, uint64_t* runGroup, hipStream_t s) {
+    if (nReads) k_run_starts<<<(nReads + 3) / 4, 256, 0, s>>>(flags, mOff, grpOff, runOff, nReads, gStart, sStart, runGroup);
 }
 void exclusive_scan_u32(const uint32_t* in, uint64_t n, uint64_t* out, void* tmp, hipStream_t s) {
     scan_impl<uint32_t>(in, n, out, (unsigned long long*)tmp, s);

@@ -53,8 +53,12 @@ struct AssignScratch {  // per match unless noted
     void* paths;           // Path
     void* comb;            // Path
     uint8_t* conn;
-    uint32_t *gFlag, *sFlag, *pathCnt;
-    uint64_t *gScan, *sScan, *gStart, *sStart;  // M + 1 entries
+    uint32_t* pathCnt;
+    uint64_t *gStart, *sStart;  // per group / per species run, + 1: its first match
+    uint64_t* runGroup;         // per species run: its first group
+    const uint8_t* runFlag;     // launch_run_flags: bit 0 a group starts here, bit 1 a species run
+    const uint32_t *grpCnt, *runCnt;  // per read
+    uint64_t *grpOff, *runOff;        // per read, + 1: their exclusive scans
     float* spScore;        // per species run
     uint64_t* waveList;    // per species run: runs queued for k_combine_wave
     uint32_t* waveCount;   // 1
@@ -79,11 +83,10 @@ inline unsigned stride_grid(uint64_t n, unsigned block = 256) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
 void exclusive_scan_u32(const uint32_t* in, uint64_t n, uint64_t* out, void* tmp, hipStream_t s);
 void exclusive_scan_u64(const uint64_t* in, uint64_t n, uint64_t* out, void* tmp, hipStream_t s);
-// K6 run index of nM sorted matches: flags nM bytes, tileSum run_index_tmp_bytes(nM); writes
-// gScan/sScan (nM + 1) and gStart/sStart (count + 1)
-uint64_t run_index_tmp_bytes(uint64_t nM);
-void launch_run_index(const mtb_match* M, uint64_t nM, uint8_t* flags, unsigned long long* tileSum, uint64_t* gScan,
-                      uint64_t* sScan, uint64_t* gStart, uint64_t* sStart, hipStream_t s);
+// K6 run index from the flag bytes of launch_run_flags and the scans of its per-read counts
+// (grpOff / runOff, n + 1): gStart (groups + 1), sStart and runGroup (runs + 1)
+void launch_run_starts(const uint8_t* flags, const uint64_t* mOff, const uint64_t* grpOff, const uint64_t* runOff,
+                       uint32_t nReads, uint64_t* gStart, uint64_t* sStart, uint64_t* runGroup, hipStream_t s);
 
 void launch_read_meta(const uint64_t* off1, const uint64_t* off2, uint32_t n, int paired, ReadMeta* meta,
                       uint32_t* qlen, uint32_t* maxW, uint32_t* readLens, hipStream_t s);
@@ -396,9 +399,11 @@ inline uint32_t prune_min_matches(int minConsCnt, int minConsCntEuk, int maxCodo
     const int need = d <= 1 ? 1 : 1 + (d - 1 + sh - 1) / sh;
     return (uint32_t)(need < 2 ? 2 : need);
 }
-// the live prefix of each segment (mOff) to out at liveOff (exclusive scan of liveCnt)
-void launch_pack_live(const mtb_match* in, const uint64_t* mOff, const uint64_t* liveOff, uint32_t nReads,
-                      mtb_match* out, int* err, hipStream_t s);
+// the live prefix of each segment (mOff) to out at liveOff (exclusive scan of liveCnt), with the K6
+// run flags (one byte per live match, at its dense index) and each read's group and run counts.
+// out == nullptr: no pruning ran, in is dense at liveOff already (flags and counts only).
+void launch_run_flags(const mtb_match* in, const uint64_t* mOff, const uint64_t* liveOff, uint32_t nReads,
+                      mtb_match* out, uint8_t* flags, uint32_t* grpCnt, uint32_t* runCnt, int* err, hipStream_t s);
 void launch_max_u32(const uint32_t* x, uint32_t n, uint32_t* out, hipStream_t s);
 void launch_max_seg(const uint64_t* off, uint32_t n, uint32_t* out, hipStream_t s);
 constexpr uint32_t kSegSortLds = 8192;
