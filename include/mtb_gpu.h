@@ -362,6 +362,38 @@ int mtb_build_db(const mtb_build_input* in, const mtb_db_host* taxonomy, const m
                  mtb_db_built* out);
 void mtb_free_built(mtb_db_built* b);
 
+/* Merge of reference DBs (updateDB, builds of several parts). */
+typedef struct mtb_merge_input {            /* one DB's k-mer files, host arrays */
+    const uint16_t* diff_idx; uint64_t n_diff_idx;
+    const uint32_t* info;     uint64_t n_info;
+} mtb_merge_input;
+
+/* IndexCreator::mergeTargetFiles<DB_CREATION> (IndexCreator.h:322-472) on the GPU: the inputs'
+ * k-mers in compareTargetKmer order (value, species, taxID), one entry per (value, species) whose
+ * info is the LCA of the group's taxIDs, encoded as mtb_build_db encodes; the split table follows
+ * the merge's rule, sizeOfSplit = (sum of the inputs' n_info) / (split_num - 1) (IndexCreator.h:343).
+ * n_in in [1, 64]; species from taxid_list (the union of the inputs' lists) as updateTaxId2SpeciesTaxId
+ * makes them. MTB_ERR_DB: an input whose terminal words differ from n_info, or a taxID without a
+ * species; MTB_ERR_UNSUPPORTED: an info entry with bit 31 set; MTB_ERR_OOM (the bytes needed in
+ * mtb_last_error) before any k-mer is uploaded when the merge does not fit the device. */
+int mtb_merge_db(const mtb_merge_input* in, int n_in,
+                 const int32_t* taxid_list, uint64_t n_taxid_list,   /* union of the inputs' lists */
+                 const mtb_db_host* taxonomy, const mtb_params* par,
+                 int split_num, int device, mtb_db_built* out);      /* release with mtb_free_built */
+
+/* The same over DB directories: equal Kmer_format, Syncmer, Reduced_alphabet and Accession_level
+ * in their db.parameters (else MTB_ERR_ARG), the taxonomy of dirs[0]; writes diffIdx, info, split,
+ * taxID_list (ascending) and db.parameters to out_dir and copies taxonomyDB or taxonomy/ (and
+ * acc2taxid.map if present) from dirs[0]. */
+int mtb_merge_db_dirs(const char* const* dirs, int n_dirs, const char* out_dir, int split_num, int device);
+
+/* Phase times of this process's last merge in ms: [0] upload + decode, [1] merge passes,
+ * [2] dedupe + LCA, [3] encode + split, [4] total (HIP events). Returns the entries written. */
+int mtb_merge_last_ms(float* ms, int n);
+
+/* Items per merge tile (so tests can straddle it). */
+uint32_t mtb_merge_tile_items(void);
+
 /* ---- host I/O around the path ------------------------------------------ */
 /* One batch of reads in the flat layout mtb_classify_batch takes; names are the header's first
  * token (kseq), concatenated, name i = names[name_off[i] .. name_off[i+1]). Buffers belong to the

@@ -25,6 +25,7 @@ EXPORTED = [
     "mtb_ctx_device", "mtb_start_classify_multi", "mtb_mask_reads", "mtb_workspace_bytes", "mtb_set_workspace_cap",
     "mtb_open_phases", "mtb_start_classify_partitioned", "mtb_release_workspace", "mtb_hamming", "mtb_memcpy",
     "mtb_line_ext_check", "mtb_link_check", "mtb_pin_eval", "mtb_sort_pairs",
+    "mtb_merge_db", "mtb_merge_db_dirs", "mtb_merge_last_ms", "mtb_merge_tile_items",
 ]
 
 
@@ -100,6 +101,10 @@ def lib() -> ctypes.CDLL:
     L.mtb_get_em_mappings.argtypes = [vp, u32, vp, u64, P(u64)]
     L.mtb_em.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp, u64, P(u64), P(MtbEmStats)]
     L.mtb_write_em_results.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, vp, u64, u32]
+    L.mtb_merge_db_dirs.argtypes = [P(ctypes.c_char_p), i32, ctypes.c_char_p, i32, i32]
+    L.mtb_merge_last_ms.argtypes = [P(ctypes.c_float), i32]
+    L.mtb_merge_tile_items.argtypes = []
+    L.mtb_merge_tile_items.restype = u32
     L.mtb_debug_tables.argtypes = [vp, vp, vp]
     L.mtb_debug_tables.restype = None
     _LIB = L

@@ -211,6 +211,108 @@ using namespace mtb;
         }                                                                                       \
     } while (0)
 
+namespace mtb {
+
+int encode_sorted_kmers(const uint64_t* sk, const uint64_t* sp_, uint64_t kept, const HostTaxonomy& T, int splitNum,
+                        uint64_t splitTotal, bool deviceOut, int kmerFormat, void* scanTmp, hipEvent_t evDedupe,
+                        hipStream_t s, mtb_db_built* out) {
+    int32_t *tNodeOf = nullptr, *tNodeTax = nullptr, *tParent = nullptr, *tDepth = nullptr;
+    uint32_t *head = nullptr, *words = nullptr, *uinfo = nullptr;
+    uint64_t *uidx = nullptr, *uval = nullptr, *woff = nullptr, *gend = nullptr;
+    uint16_t* dDiff = nullptr;
+    void* ownTmp = nullptr;
+    uint64_t U = 0, NW = 0, sizeOfSplit = 0;
+    std::vector<uint64_t> ge;
+    int rc = MTB_ERR_HIP;
+    if (!scanTmp) {
+        HIP_B(hipMalloc(&ownTmp, 8 * scan_tmp_elems(kept + 2)));
+        scanTmp = ownTmp;
+    }
+    {
+        const std::vector<int32_t>* arrs[4] = {&T.nodeOf, &T.nodeTax, &T.parent, &T.depth};
+        int32_t** dst[4] = {&tNodeOf, &tNodeTax, &tParent, &tDepth};
+        for (int a = 0; a < 4; a++) {
+            HIP_B(hipMalloc(dst[a], 4 * arrs[a]->size() + 4));
+            HIP_B(hipMemcpyAsync(*dst[a], arrs[a]->data(), 4 * arrs[a]->size(), hipMemcpyHostToDevice, s));
+        }
+    }
+    HIP_B(hipMalloc(&head, 4 * (kept + 1)));
+    HIP_B(hipMalloc(&uidx, 8 * (kept + 1)));
+    if (kept) k_group_heads<<<stride_grid(kept), 256, 0, s>>>(sk, sp_, kept, head);
+    exclusive_scan_u32(head, kept, uidx, scanTmp, s);
+    HIP_B(hipMemcpyAsync(&U, uidx + kept, 8, hipMemcpyDeviceToHost, s));
+    HIP_B(hipStreamSynchronize(s));
+    HIP_B(hipMalloc(&uval, 8 * (U + kDbPad)));
+    HIP_B(hipMalloc(&uinfo, 4 * (U + kDbPad)));
+    if (kept)
+        k_group_reduce<<<stride_grid(kept), 256, 0, s>>>(
+            sk, sp_, kept, head, uidx, TaxLca{tNodeOf, tNodeTax, tParent, tDepth, T.maxTax}, uval, uinfo);
+    if (evDedupe) HIP_B(hipEventRecord(evDedupe, s));
+    if (deviceOut) {  // resident form for mtb_open_resident; no diffIdx / split
+        if (kmerFormat == 2) launch_to_rank_form(uval, U, s);
+        HIP_B(hipStreamSynchronize(s));
+        out->dev_values = uval;
+        out->dev_info = uinfo;
+        out->n_info = U;
+        uval = nullptr;
+        uinfo = nullptr;
+        rc = MTB_OK;
+        goto fail;
+    }
+    // diffIdx words (the group heads and indices are done with: a merge's peak is here)
+    HIP_B(hipFree(head));
+    head = nullptr;
+    HIP_B(hipFree(uidx));
+    uidx = nullptr;
+    HIP_B(hipMalloc(&words, 4 * (U + 1)));
+    HIP_B(hipMalloc(&woff, 8 * (U + 1)));
+    if (U) k_count_words<<<stride_grid(U), 256, 0, s>>>(uval, U, words);
+    exclusive_scan_u32(words, U, woff, scanTmp, s);
+    HIP_B(hipMemcpyAsync(&NW, woff + U, 8, hipMemcpyDeviceToHost, s));
+    HIP_B(hipStreamSynchronize(s));
+    HIP_B(hipMalloc(&dDiff, 2 * (NW + 1)));
+    if (U) k_write_words<<<stride_grid(U), 256, 0, s>>>(uval, U, woff, dDiff);
+    // split table: the distinct first-AA-change indices after every sizeOfSplit k-mers, sizeOfSplit =
+    // uniqKmerCnt / (splitNum - 1) in a build, numOfKmerBeforeMerge / (splitNum - 1) in a merge
+    sizeOfSplit = splitNum > 1 ? (splitTotal == kSplitByUnique ? U : splitTotal) / (uint64_t)(splitNum - 1) : 0;
+    HIP_B(hipMalloc(&gend, 8 * (size_t)std::max(1, splitNum)));
+    if (splitNum > 1) k_split_ends<<<(splitNum + 255) / 256, 256, 0, s>>>(uval, U, sizeOfSplit, splitNum, gend);
+    ge.assign((size_t)std::max(0, splitNum - 1), U);
+    if (!ge.empty()) HIP_B(hipMemcpyAsync(ge.data(), gend, 8 * ge.size(), hipMemcpyDeviceToHost, s));
+    out->n_diff_idx = NW;
+    out->n_info = U;
+    out->diff_idx = (uint16_t*)malloc(2 * NW + 2);
+    out->info = (uint32_t*)malloc(4 * U + 4);
+    HIP_B(hipMemcpyAsync(out->diff_idx, dDiff, 2 * NW, hipMemcpyDeviceToHost, s));
+    HIP_B(hipMemcpyAsync(out->info, uinfo, 4 * U, hipMemcpyDeviceToHost, s));
+    HIP_B(hipStreamSynchronize(s));
+    {
+        out->n_split = (uint64_t)std::max(1, splitNum);
+        out->split = (uint64_t*)calloc(3 * out->n_split, sizeof(uint64_t));
+        uint64_t idx = 1, last = ~0ull;
+        for (uint64_t g : ge) {
+            if (g >= U || g == last) continue;
+            last = g;
+            uint64_t val = 0, wo = 0;
+            HIP_B(hipMemcpy(&val, uval + g, 8, hipMemcpyDeviceToHost));
+            HIP_B(hipMemcpy(&wo, woff + g + 1, 8, hipMemcpyDeviceToHost));
+            out->split[3 * idx + 0] = val;
+            out->split[3 * idx + 1] = wo;
+            out->split[3 * idx + 2] = g + 1;
+            idx++;
+        }
+    }
+    rc = MTB_OK;
+fail:
+    void* frees[] = {tNodeOf, tNodeTax, tParent, tDepth, head, words, uinfo, uidx, uval, woff, gend, dDiff, ownTmp};
+    hipStreamSynchronize(s);
+    for (void* p : frees)
+        if (p) hipFree(p);
+    return rc;
+}
+
+}  // namespace mtb
+
 extern "C" {
 
 void mtb_free_built(mtb_db_built* b) {
@@ -252,19 +354,14 @@ int mtb_build_db(const mtb_build_input* in, const mtb_db_host* taxo, const mtb_p
     uint8_t* dSeq = nullptr;
     uint64_t *dOff = nullptr, *dW = nullptr, *dSlot = nullptr, *kA = nullptr, *pA = nullptr, *kB = nullptr, *pB = nullptr;
     int32_t *dBg = nullptr, *dBs = nullptr, *dBe = nullptr, *dBst = nullptr, *dTax = nullptr, *dSp = nullptr;
-    int32_t *tNodeOf = nullptr, *tNodeTax = nullptr, *tParent = nullptr, *tDepth = nullptr;
-    uint32_t *counts = nullptr, *head = nullptr, *words = nullptr, *uinfo = nullptr;
-    uint64_t *offs = nullptr, *uidx = nullptr, *uval = nullptr, *woff = nullptr, *gend = nullptr;
-    uint16_t* dDiff = nullptr;
+    uint32_t* counts = nullptr;
+    uint64_t* offs = nullptr;
     void* scanTmp = nullptr;
-    uint64_t R = 0, kept = 0, U = 0, NW = 0;
+    uint64_t R = 0, kept = 0;
     bool inB1 = false, inB2 = false;
     uint64_t *sk, *sp_;
     int rc = MTB_ERR_HIP;
-    std::vector<uint64_t> ge;
-    std::vector<uint64_t> splitHost;
     int spBits = 1;
-    uint64_t sizeOfSplit = 0;
 
     HIP_B(hipSetDevice(device));
     HIP_B(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -323,76 +420,11 @@ int mtb_build_db(const mtb_build_input* in, const mtb_db_host* taxo, const mtb_p
         sk = inB2 ? k2 : k1;
         sp_ = inB2 ? p2 : p1;
     }
-    // dedup per (value, species) with the LCA of the group's taxIDs
-    {
-        std::vector<int32_t>* arrs[4] = {&T.nodeOf, &T.nodeTax, &T.parent, &T.depth};
-        int32_t** dst[4] = {&tNodeOf, &tNodeTax, &tParent, &tDepth};
-        for (int a = 0; a < 4; a++) {
-            HIP_B(hipMalloc(dst[a], 4 * arrs[a]->size() + 4));
-            HIP_B(hipMemcpyAsync(*dst[a], arrs[a]->data(), 4 * arrs[a]->size(), hipMemcpyHostToDevice, s));
-        }
-    }
-    HIP_B(hipMalloc(&head, 4 * (kept + 1)));
-    HIP_B(hipMalloc(&uidx, 8 * (kept + 1)));
-    if (kept) k_group_heads<<<stride_grid(kept), 256, 0, s>>>(sk, sp_, kept, head);
-    exclusive_scan_u32(head, kept, uidx, scanTmp, s);
-    HIP_B(hipMemcpyAsync(&U, uidx + kept, 8, hipMemcpyDeviceToHost, s));
-    HIP_B(hipStreamSynchronize(s));
-    HIP_B(hipMalloc(&uval, 8 * (U + kDbPad)));
-    HIP_B(hipMalloc(&uinfo, 4 * (U + kDbPad)));
-    if (kept)
-        k_group_reduce<<<stride_grid(kept), 256, 0, s>>>(
-            sk, sp_, kept, head, uidx, TaxLca{tNodeOf, tNodeTax, tParent, tDepth, T.maxTax}, uval, uinfo);
-    if (in->flags & MTB_BUILD_DEVICE_OUT) {  // resident form for mtb_open_resident; no diffIdx / split
-        if (par->kmer_format == 2) launch_to_rank_form(uval, U, s);
-        HIP_B(hipStreamSynchronize(s));
-        out->dev_values = uval;
-        out->dev_info = uinfo;
-        out->n_info = U;
-        uval = nullptr;
-        uinfo = nullptr;
-        goto taxids;
-    }
-    // diffIdx words
-    HIP_B(hipMalloc(&words, 4 * (U + 1)));
-    HIP_B(hipMalloc(&woff, 8 * (U + 1)));
-    if (U) k_count_words<<<stride_grid(U), 256, 0, s>>>(uval, U, words);
-    exclusive_scan_u32(words, U, woff, scanTmp, s);
-    HIP_B(hipMemcpyAsync(&NW, woff + U, 8, hipMemcpyDeviceToHost, s));
-    HIP_B(hipStreamSynchronize(s));
-    HIP_B(hipMalloc(&dDiff, 2 * (NW + 1)));
-    if (U) k_write_words<<<stride_grid(U), 256, 0, s>>>(uval, U, woff, dDiff);
-    // split table: the distinct first-AA-change indices after every uniqKmerCnt/(splitNum-1) k-mers
-    sizeOfSplit = in->split_num > 1 ? U / (uint64_t)(in->split_num - 1) : 0;
-    HIP_B(hipMalloc(&gend, 8 * (size_t)std::max(1, in->split_num)));
-    if (in->split_num > 1)
-        k_split_ends<<<(in->split_num + 255) / 256, 256, 0, s>>>(uval, U, sizeOfSplit, in->split_num, gend);
-    ge.assign((size_t)std::max(0, in->split_num - 1), U);
-    if (!ge.empty()) HIP_B(hipMemcpyAsync(ge.data(), gend, 8 * ge.size(), hipMemcpyDeviceToHost, s));
-    out->n_diff_idx = NW;
-    out->n_info = U;
-    out->diff_idx = (uint16_t*)malloc(2 * NW + 2);
-    out->info = (uint32_t*)malloc(4 * U + 4);
-    HIP_B(hipMemcpyAsync(out->diff_idx, dDiff, 2 * NW, hipMemcpyDeviceToHost, s));
-    HIP_B(hipMemcpyAsync(out->info, uinfo, 4 * U, hipMemcpyDeviceToHost, s));
-    HIP_B(hipStreamSynchronize(s));
-    {
-        out->n_split = (uint64_t)std::max(1, in->split_num);
-        out->split = (uint64_t*)calloc(3 * out->n_split, sizeof(uint64_t));
-        uint64_t idx = 1, last = ~0ull;
-        for (uint64_t g : ge) {
-            if (g >= U || g == last) continue;
-            last = g;
-            uint64_t val = 0, wo = 0;
-            HIP_B(hipMemcpy(&val, uval + g, 8, hipMemcpyDeviceToHost));
-            HIP_B(hipMemcpy(&wo, woff + g + 1, 8, hipMemcpyDeviceToHost));
-            out->split[3 * idx + 0] = val;
-            out->split[3 * idx + 1] = wo;
-            out->split[3 * idx + 2] = g + 1;
-            idx++;
-        }
-    }
-taxids:
+    // dedup per (value, species) with the LCA of the group's taxIDs, then diffIdx / info / split
+    rc = encode_sorted_kmers(sk, sp_, kept, T, in->split_num, kSplitByUnique, (in->flags & MTB_BUILD_DEVICE_OUT) != 0,
+                             par->kmer_format, scanTmp, nullptr, s, out);
+    if (rc != MTB_OK) goto fail;
+    rc = MTB_ERR_HIP;
     {
         std::vector<int32_t> ids(in->genome_taxid, in->genome_taxid + in->n_genomes);
         std::sort(ids.begin(), ids.end());
@@ -403,8 +435,7 @@ taxids:
     }
     rc = MTB_OK;
 fail:
-    void* frees[] = {dW, dSlot, kA, pA, kB, pB, dBg, dBs, dBe, dBst, dTax, dSp, tNodeOf, tNodeTax, tParent, tDepth,
-                     counts, head, words, uinfo, offs, uidx, uval, woff, gend, dDiff, scanTmp};
+    void* frees[] = {dW, dSlot, kA, pA, kB, pB, dBg, dBs, dBe, dBst, dTax, dSp, counts, offs, scanTmp};
     if (s) hipStreamSynchronize(s);
     for (void* p : frees)
         if (p) hipFree(p);

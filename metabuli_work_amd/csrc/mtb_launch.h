@@ -448,6 +448,24 @@ void launch_em_reclassify(const float* score, const uint32_t* spIdx, const int32
                           const uint32_t* qId, uint64_t nQ, const double* p, const double* lf, const TaxDevice& t,
                           mtb_em_read* out, hipStream_t s);
 
+// ---- DB construction: the tail mtb_build_db and mtb_merge_db share (mtb_build.hip) --------------
+// kept device pairs sorted by (value, species), payload = species << 32 | taxID: one entry per
+// (value, species) with the LCA of the group's taxIDs (filterKmers<DB_CREATION>), then diffIdx, info
+// and the split table into out's host arrays, or with deviceOut the resident-form values + info
+// into out->dev_*. The split's sizeOfSplit is splitTotal / (splitNum - 1): kSplitByUnique takes the
+// unique count (writeTargetFilesAndSplits, IndexCreator.cpp:819), a merge passes its k-mer count
+// before merging (IndexCreator.h:343). scanTmp: scan_tmp_elems(kept + 2) u64, or null (allocated
+// here). evDedupe (nullable): recorded after the dedupe + LCA. Returns MTB_OK or an error code
+// (set_error called); out's taxid_list is left to the caller.
+struct HostTaxonomy;
+constexpr uint64_t kSplitByUnique = ~0ull;
+int encode_sorted_kmers(const uint64_t* keys, const uint64_t* pay, uint64_t kept, const HostTaxonomy& T, int splitNum,
+                        uint64_t splitTotal, bool deviceOut, int kmerFormat, void* scanTmp, hipEvent_t evDedupe,
+                        hipStream_t s, mtb_db_built* out);
+// Items per tile of the two-way merge (mtb_merge.hip)
+constexpr uint32_t kMergeDbPer = 8;
+constexpr uint32_t kMergeDbTile = 256 * kMergeDbPer;
+
 // ---- K0M: tantan low-complexity masking of the reads (mtb_mask.hip; --mask-residues 1) ----------
 constexpr int kTantanOffsets = 50;  // tantan's maxCycleLength (SeqIterator.cpp:163)
 struct TantanTables {

@@ -2,7 +2,9 @@
 
 ``build_db`` runs the GPU builder (mtb_build_db, csrc/mtb_build.hip): genomes + gene blocks +
 taxonomy -> diffIdx / info / split / taxID_list in the reference's on-disk format
-(IndexCreator.cpp:316-376,811-886). ``HostDb`` keeps the arrays (and the numpy buffers the C
+(IndexCreator.cpp:316-376,811-886). ``merge_dbs`` / ``merge_db_dirs`` / ``update_db`` run the GPU
+merge (mtb_merge_db, csrc/mtb_merge.hip: IndexCreator::mergeTargetFiles<DB_CREATION>), the second
+half of the reference's updateDB and of its builds of several flushes. ``HostDb`` keeps the arrays (and the numpy buffers the C
 structs point into) alive, can write them as a DB directory, and yields the ``mtb_db_host``
 struct that mtb_open_host / the oracle consume.
 """
@@ -31,6 +33,11 @@ class MtbDbBuilt(ctypes.Structure):
                 ("split", ctypes.c_void_p), ("n_split", ctypes.c_uint64),
                 ("taxid_list", ctypes.c_void_p), ("n_taxid_list", ctypes.c_uint64),
                 ("dev_values", ctypes.c_void_p), ("dev_info", ctypes.c_void_p)]
+
+
+class MtbMergeInput(ctypes.Structure):
+    _fields_ = [("diff_idx", ctypes.c_void_p), ("n_diff_idx", ctypes.c_uint64),
+                ("info", ctypes.c_void_p), ("n_info", ctypes.c_uint64)]
 
 
 MTB_BUILD_DEVICE_OUT = 8
@@ -122,19 +129,14 @@ def _lib_build():
     L.mtb_build_db.argtypes = [ctypes.POINTER(MtbBuildInput), ctypes.POINTER(MtbDbHost), ctypes.POINTER(MtbParams),
                                ctypes.c_int, ctypes.POINTER(MtbDbBuilt)]
     L.mtb_free_built.argtypes = [ctypes.POINTER(MtbDbBuilt)]
+    L.mtb_merge_db.argtypes = [ctypes.POINTER(MtbMergeInput), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                               ctypes.POINTER(MtbDbHost), ctypes.POINTER(MtbParams), ctypes.c_int, ctypes.c_int,
+                               ctypes.POINTER(MtbDbBuilt)]
     return L
 
 
-def build_db(gen, taxo, par: MtbParams, device: int = 0, split_num: int = 4096, device_seq=None) -> HostDb:
-    """Build the reference DB on the GPU. ``device_seq`` = (seq, off) torch tensors already in HBM
-    (bench path); otherwise ``gen.seq`` / ``gen.off`` are uploaded."""
-    hdb = HostDb(taxo)
-    inp, keep = _build_input(gen, device_seq, split_num, 0)
-    out = MtbDbBuilt()
-    L = _lib_build()
-    tax_struct = hdb.c_struct()
-    check(L.mtb_build_db(ctypes.byref(inp), ctypes.byref(tax_struct), ctypes.byref(par), device, ctypes.byref(out)),
-          "mtb_build_db")
+def _take_built(hdb: "HostDb", out: MtbDbBuilt, L) -> "HostDb":
+    """The malloc'd arrays of a mtb_db_built copied into hdb; the struct is released."""
     try:
         def arr(p, n, dt):
             if n == 0:
@@ -148,6 +150,109 @@ def build_db(gen, taxo, par: MtbParams, device: int = 0, split_num: int = 4096, 
     finally:
         L.mtb_free_built(ctypes.byref(out))
     return hdb
+
+
+def subset_genomes(gen, idx):
+    """The genomes ``idx`` (indices into ``gen``) with their gene blocks, as a Genomes of their own."""
+    idx = np.asarray(idx, np.int64)
+    off = np.asarray(gen.off, np.uint64)
+    new_off = np.zeros(len(idx) + 1, np.uint64)
+    new_off[1:] = np.cumsum(off[idx + 1] - off[idx])
+    seq = (np.concatenate([gen.seq[int(off[g]):int(off[g + 1])] for g in idx]) if len(idx)
+           else np.zeros(0, np.uint8))
+    new_of = np.full(len(off) - 1, -1, np.int64)
+    new_of[idx] = np.arange(len(idx))
+    blk = new_of[np.asarray(gen.blk_genome, np.int64)]
+    keep = blk >= 0
+    order = np.argsort(blk[keep], kind="stable")
+
+    def pick(a):
+        return np.ascontiguousarray(np.asarray(a)[keep][order], np.int32)
+    return type(gen)(np.ascontiguousarray(seq, np.uint8), new_off, np.ascontiguousarray(gen.taxid[idx], np.int32),
+                     np.ascontiguousarray(gen.species[idx], np.int32), blk[keep][order].astype(np.int32),
+                     pick(gen.blk_start), pick(gen.blk_end), pick(gen.blk_strand))
+
+
+def build_db(gen, taxo, par: MtbParams, device: int = 0, split_num: int = 4096, device_seq=None,
+             parts: int = 1) -> HostDb:
+    """Build the reference DB on the GPU. ``device_seq`` = (seq, off) torch tensors already in HBM
+    (bench path); otherwise ``gen.seq`` / ``gen.off`` are uploaded. ``parts`` = k > 1: the genomes
+    are built in k groups (genome g in group g % k) and the k DBs merged, the reference's build of
+    several flushes (numOfFlush > 1): diffIdx and info equal the single build's, the split table
+    follows the merge's rule (see ``merge_dbs``)."""
+    if parts > 1:
+        if device_seq is not None:
+            raise ValueError("parts > 1 builds from host genomes")
+        groups = [np.arange(len(gen.taxid))[k::parts] for k in range(parts)]
+        dbs = [build_db(subset_genomes(gen, g), taxo, par, device, split_num) for g in groups if len(g)]
+        return merge_dbs(dbs, taxo, par, device, split_num)
+    hdb = HostDb(taxo)
+    inp, keep = _build_input(gen, device_seq, split_num, 0)
+    out = MtbDbBuilt()
+    L = _lib_build()
+    tax_struct = hdb.c_struct()
+    check(L.mtb_build_db(ctypes.byref(inp), ctypes.byref(tax_struct), ctypes.byref(par), device, ctypes.byref(out)),
+          "mtb_build_db")
+    return _take_built(hdb, out, L)
+
+
+def merge_dbs(dbs, taxo, par: MtbParams, device: int = 0, split_num: int = 4096) -> HostDb:
+    """Merge reference DBs on the GPU (mtb_merge_db): the k-mers of ``dbs`` (HostDb, 1 to 64 of them)
+    in (value, species, taxID) order, one entry per (value, species) with the LCA of its taxIDs; the
+    taxID list is the sorted union of theirs. diffIdx and info equal those of one build over all
+    the genomes; the split table is sized by the k-mer count before merging
+    (IndexCreator.h:343), unlike a single build's (IndexCreator.cpp:819)."""
+    hdb = HostDb(taxo)
+    L = _lib_build()
+    ins = (MtbMergeInput * max(1, len(dbs)))()
+    keep = []
+    for i, d in enumerate(dbs):
+        di, inf = np.ascontiguousarray(d.diff_idx, np.uint16), np.ascontiguousarray(d.info, np.uint32)
+        keep += [di, inf]
+        ins[i].diff_idx, ins[i].n_diff_idx = di.ctypes.data, len(di)
+        ins[i].info, ins[i].n_info = inf.ctypes.data, len(inf)
+    ids = [np.asarray(d.taxid_list, np.int32) for d in dbs if d.taxid_list is not None]
+    union = np.unique(np.concatenate(ids)).astype(np.int32) if ids else np.zeros(0, np.int32)
+    out = MtbDbBuilt()
+    tax_struct = hdb.c_struct()
+    check(L.mtb_merge_db(ins, len(dbs), union.ctypes.data, len(union), ctypes.byref(tax_struct), ctypes.byref(par),
+                         split_num, device, ctypes.byref(out)), "mtb_merge_db")
+    return _take_built(hdb, out, L)
+
+
+def merge_db_dirs(dirs, out_dir: str, device: int = 0, split_num: int = 4096) -> None:
+    """Merge DB directories into ``out_dir`` (mtb_merge_db_dirs): their db.parameters must agree in
+    Kmer_format, Syncmer, Reduced_alphabet and Accession_level; taxonomy and db.parameters come
+    from ``dirs[0]``."""
+    arr = (ctypes.c_char_p * len(dirs))(*[os.fsencode(d) for d in dirs])
+    check(lib().mtb_merge_db_dirs(arr, len(dirs), os.fsencode(out_dir), split_num, device), "mtb_merge_db_dirs")
+
+
+def load_db_dir(directory: str, taxo) -> HostDb:
+    """diffIdx / info / split / taxID_list of a DB directory as a HostDb over ``taxo``."""
+    def rd(name, dt):
+        return np.fromfile(os.path.join(directory, name), dtype=dt)
+    ids = np.loadtxt(os.path.join(directory, "taxID_list"), dtype=np.int32, ndmin=1)
+    return HostDb(taxo, rd("diffIdx", np.uint16), rd("info", np.uint32), rd("split", np.uint64), ids)
+
+
+def update_db(old_dir: str, gen, taxo, par: MtbParams, out_dir: str, device: int = 0, split_num: int = 4096) -> HostDb:
+    """Add the genomes ``gen`` to the DB in ``old_dir`` and write the result to ``out_dir``: the
+    reference's updateDB (updateDB.cpp:134-142) without --new-taxa: the new genomes' DB is built,
+    then merged with the old diffIdx / info over the union of the taxID lists. ``taxo`` holds the
+    old DB's taxa and the new genomes'."""
+    new = build_db(gen, taxo, par, device, split_num)
+    merged = merge_dbs([load_db_dir(old_dir, taxo), new], taxo, par, device, split_num)
+    merged.write(out_dir, par)
+    return merged
+
+
+def merge_last_ms():
+    """Phase times of this process's last merge in ms: upload + decode, merge passes, dedupe + LCA,
+    encode + split, total."""
+    ms = (ctypes.c_float * 5)()
+    check(lib().mtb_merge_last_ms(ms, 5), "mtb_merge_last_ms")
+    return [float(x) for x in ms]
 
 
 _HIP = None
