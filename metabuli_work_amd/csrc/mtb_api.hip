@@ -162,6 +162,7 @@ struct mtb_ctx {
     uint32_t spillShift = 0;     // MTB_DIRECT=3: read stretches taken as a quarter (queries spill; tests)
     bool sparse = false;         // the batch's matches are still in the direct join's layout (mDirect, slotOff * chunkC)
     uint32_t maxW = 0;           // the batch's most windows in one frame of one read
+    uint32_t maxMate = 0;        // the batch's longest mate past kSeqMate bases (0: none; launch_read_meta)
     int sortLoFine = kQuerySortLoFine;  // MTB_SORT_LO_FINE (experiments)
     bool forceGeneric = false;   // MTB_FORCE_GENERIC=1: fast paths off, fallbacks only (tests)
     bool segsortGlobal = false;  // MTB_SEGSORT_GLOBAL=1: every K5 segment through global scratch (tests)
@@ -1120,9 +1121,11 @@ static int join_stage(mtb_ctx* c, const uint8_t* dSeq1, const uint64_t* dOff1, c
                                       c->par.smer_len, c->unitInfo.as<uint64_t>(), c->lines, c->keysB.as<uint64_t>(),
                                       c->valsB.as<uint32_t>(), c->mTotal.as<unsigned long long>(), c->rankLo,
                                       c->rankHi, &c->Qall, cap, c->filterThreadMajor, s,
-                                      digits ? c->digA.as<uint8_t>() : nullptr, nullptr, 0, nullptr, c->upr, c->link);
+                                      digits ? c->digA.as<uint8_t>() : nullptr, nullptr, 0, nullptr, c->upr, c->link,
+                                      c->maxMate <= kSeqMate);
             HIP_TRY(hipGetLastError());
-            if (Q == ~0ull) {  // launch_extract_filter's flag: a block's bases past K1F's LDS stage
+            if (Q == ~0ull) {  // launch_extract_filter's flag: a block's bases past K1F's LDS stage (a guard:
+                               // a batch with a mate past kSeqMate bases is not staged)
                 set_error("internal error: K1F sequence stage overflow");
                 return MTB_ERR_INTERNAL;
             }
@@ -1602,14 +1605,16 @@ static int classify_batch(mtb_ctx* c, const char* seq, const uint64_t* off, cons
     HIP_TRY(c->reserve.ensure(sizeof(uint32_t) * (n + 1)));
     HIP_TRY(c->slotOff.ensure(sizeof(uint64_t) * (n + 1)));
     HIP_TRY(c->qlen.ensure(sizeof(uint32_t) * (n + 1)));
-    HIP_TRY(c->maxSeg.ensure(sizeof(uint32_t)));
+    HIP_TRY(c->maxSeg.ensure(2 * sizeof(uint32_t)));
     HIP_TRY(c->scanTmp.ensure(sizeof(uint64_t) * scan_tmp_elems(n + 1)));
     HIP_TRY(c->readLens.ensure(sizeof(uint32_t) * (n + 1)));
     launch_read_meta(dOff1, dOff2, n, paired, c->meta.as<ReadMeta>(), c->qlen.as<uint32_t>(), c->maxSeg.as<uint32_t>(),
                      c->readLens.as<uint32_t>(), s);
-    uint32_t maxW = 0;
-    HIP_TRY(hipMemcpyAsync(&maxW, c->maxSeg.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    uint32_t metaMax[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(metaMax, c->maxSeg.p, sizeof(metaMax), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t maxW = metaMax[0];
+    c->maxMate = metaMax[1];
     // chunk = the longest frame when it is short (no padding for uniform short reads), else 64
     const uint32_t C = std::min<uint32_t>(std::max<uint32_t>(maxW, 1), 64);
     c->maxW = maxW;

@@ -173,7 +173,9 @@ void exclusive_scan_u64(const uint64_t* in, uint64_t n, uint64_t* out, void* tmp
 // ------------------------------------------------------------------------------------------------
 // K0 read metadata: loadChunkOfReads (KmerExtractor.cpp:442-494). Per read: covered lengths and
 // windows per frame of each mate (0 when the read is dropped by the shared empty rule); the batch
-// maximum sizes K1's chunks.
+// maximum sizes K1's chunks. maxW[1]: the longest mate past kSeqMate bases (0 when there is none) — a
+// pair dropped by the empty rule adds nothing to maxW[0] whatever its other mate's length, so a batch
+// can be uniform and still hold a mate that K1F's LDS stage has no room for (launch_extract_filter).
 // ------------------------------------------------------------------------------------------------
 __global__ void k_read_meta(const uint64_t* __restrict__ off1, const uint64_t* __restrict__ off2, uint32_t n,
                             int paired, ReadMeta* __restrict__ meta, uint32_t* __restrict__ qlen,
@@ -202,6 +204,8 @@ __global__ void k_read_meta(const uint64_t* __restrict__ off1, const uint64_t* _
     readLens[i] = (uint32_t)min(len1, 0xFFFF) | (uint32_t)min(len2, 0xFFFF) << 16;
     const uint32_t w = (uint32_t)max(m.w1, m.w2);
     if (w) atomicMax(maxW, w);
+    const uint32_t big = (uint32_t)max(len1, len2);
+    if (big > kSeqMate) atomicMax(maxW + 1, big);
 }
 
 // K1 work units per read: each (mate, frame) is cut into chunks of C windows. Uniform units (upr > 0:
@@ -224,7 +228,7 @@ __global__ void k_unit_read(const uint64_t* __restrict__ uOff, uint32_t n, uint3
 
 void launch_read_meta(const uint64_t* off1, const uint64_t* off2, uint32_t n, int paired, ReadMeta* meta,
                       uint32_t* qlen, uint32_t* maxW, uint32_t* readLens, hipStream_t s) {
-    hipMemsetAsync(maxW, 0, sizeof(uint32_t), s);
+    hipMemsetAsync(maxW, 0, 2 * sizeof(uint32_t), s);
     if (n == 0) return;
     k_read_meta<<<(n + 255) / 256, 256, 0, s>>>(off1, off2, n, paired, meta, qlen, maxW, readLens);
 }
@@ -2853,7 +2857,8 @@ constexpr uint32_t kBinStage = 2560;  // binned K1F: windows per group staged in
 // probes issued after its scan instead of as each window's (pair's) key is known. kSeqLds (uniform units
 // only): the block's reads' bases staged in LDS first, so the scan loads nothing from HBM — a load's
 // wait counter drains in issue order, and a base load issued behind a probe waits for that probe
-constexpr uint32_t kSeqStage = 10240;  // >= 23 read pairs (or 44 single reads) of <= 219 bp: a uniform batch's block
+// (kSeqStage bytes, mtb_launch.h: 23 read pairs or 44 single reads of at most kSeqMate bases; the launcher takes
+// this form only when no mate of the batch is longer)
 // kWavePack (MTB_K1F_WAVEPACK=1, A/B): each wave packs its own present windows with its own counter
 // atomic per group — no block barrier per group (the K4 finding: a block's waves held at a barrier
 // wait for its slowest lane's random reads)
@@ -2911,7 +2916,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLink 
                 seqAt = (u - r * upr) >= 6u ? sSeq + n1 + (off2[r] - a2) : sSeq + (off1[r] - a1);
             }
         } else if (threadIdx.x == 0) {
-            // cannot happen in a uniform batch (mates <= 219 bp); flagged in the emitted count, never silent
+            // a guard: the launcher takes this form only for a batch whose mates are all at most kSeqMate
+            // bases (a uniform batch may hold longer ones, in pairs whose other mate has no window: those
+            // batches read their bases from HBM). Flagged in the emitted count, never silent
             atomicOr(counter + 1, 1ull << 63);
         }
     }
@@ -3161,7 +3168,7 @@ uint64_t launch_extract_filter(const uint8_t* seq1, const uint64_t* off1, const 
                                unsigned long long* counter, uint64_t rankLo, uint64_t rankHi, uint64_t* emitted,
                                uint64_t cap, bool threadMajor, hipStream_t s, uint8_t* qdig,
                                unsigned long long* binCnt, uint64_t binRc, uint64_t* binHost, uint32_t upr,
-                               const uint64_t* link) {
+                               const uint64_t* link, bool seqFits) {
     if (binRc) {
         // binned output: the writes go to 2048 regions of binRc slots; the bucket counts come back
         threadMajor = false;
@@ -3201,9 +3208,10 @@ uint64_t launch_extract_filter(const uint8_t* seq1, const uint64_t* off1, const 
         unitInfo, lines, qkey, qslot, counter, rankLo, rankHi, cap, qdig, binCnt, binRc, upr, link, emitBlock)
             const char* wp = getenv("MTB_K1F_WAVEPACK");  // A/B, read per batch
             const bool wavePack = wp && atoi(wp) != 0;
-            // the bases staged in LDS (uniform batches; MTB_K1F_SEQ_LDS=0, A/B: read from HBM)
+            // the bases staged in LDS (uniform batches with no mate past kSeqMate bases; MTB_K1F_SEQ_LDS=0,
+            // A/B: read from HBM)
             const char* sl = getenv("MTB_K1F_SEQ_LDS");
-            const bool seqLds = upr && (!sl || atoi(sl) != 0);
+            const bool seqLds = upr && seqFits && (!sl || atoi(sl) != 0);
             if (seqLds && wavePack && f == "w4i")
                 k_extract_filter<16, true, false, 4, false, true, true><<<blocks, 256, lds, s>>>(
                     seq1, off1, seq2, off2, meta, uOff, unitRead, nUnits, C, extract_tables(t), kmerFormat, syncmer,
@@ -3232,7 +3240,7 @@ uint64_t launch_extract_filter(const uint8_t* seq1, const uint64_t* off1, const 
     hipMemcpyAsync(Q, counter, sizeof(Q), hipMemcpyDeviceToHost, s);
     if (binRc) hipMemcpyAsync(binHost, binCnt, kSortBins * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
     hipStreamSynchronize(s);
-    if (Q[1] >> 63) {  // a block's bases past the LDS stage (kSeqLds): never expected in a uniform batch
+    if (Q[1] >> 63) {  // a block's bases past the LDS stage (kSeqLds): a caller that passed seqFits for longer mates
         fprintf(stderr, "[mtb] internal error: K1F sequence stage overflow\n");
         Q[1] &= ~(1ull << 63);
         *emitted = ~0ull;

@@ -88,6 +88,16 @@ void exclusive_scan_u64(const uint64_t* in, uint64_t n, uint64_t* out, void* tmp
 void launch_run_starts(const uint8_t* flags, const uint64_t* mOff, const uint64_t* grpOff, const uint64_t* runOff,
                        uint32_t nReads, uint64_t* gStart, uint64_t* sStart, uint64_t* runGroup, hipStream_t s);
 
+// K1F's LDS stage for a block's bases (k_extract_filter, kSeqLds) and the longest mate it is sized for.
+// A block of 256 units touches at most 23 read pairs (12 units each) or 44 single reads (6 units), so
+// with every mate of the batch at most kSeqMate bases a block's bases fit the stage. A uniform batch's
+// mates that hold windows are at most 217 bases (64 windows per frame); only a mate of a pair the empty
+// rule drops can be longer, and launch_read_meta reports it.
+constexpr uint32_t kSeqStage = 10240;
+constexpr uint32_t kSeqMate = 219;
+static_assert(23 * 2 * kSeqMate <= kSeqStage && 44 * kSeqMate <= kSeqStage, "a uniform block's bases fit the stage");
+// maxW: 2 device words — [0] the most windows in one frame of one read, [1] the longest mate past
+// kSeqMate bases (0: none)
 void launch_read_meta(const uint64_t* off1, const uint64_t* off2, uint32_t n, int paired, ReadMeta* meta,
                       uint32_t* qlen, uint32_t* maxW, uint32_t* readLens, hipStream_t s);
 // upr > 0: uniform units (every read upr units, one per (mate, frame); k_read_units)
@@ -226,6 +236,8 @@ void launch_link_check(const ProbeLine* lines, const uint64_t* link, unsigned lo
 // reads (returns Q; *emitted = non-blank windows); unitInfo as launch_extract's. Only the first
 // `cap` present windows are written: Q > cap means the output must grow and the pass rerun.
 // threadMajor (A/B): round 3's output order (each thread's present windows together).
+// seqFits: every mate of the batch is at most kSeqMate bases, so a uniform batch's blocks may stage
+// their bases in LDS; false sends a uniform batch through the form that reads them from HBM.
 uint64_t launch_extract_filter(const uint8_t* seq1, const uint64_t* off1, const uint8_t* seq2, const uint64_t* off2,
                                const ReadMeta* meta, const uint64_t* uOff, const uint32_t* unitRead, uint64_t nUnits,
                                uint32_t C, const HostTables& t, int kmerFormat, int syncmer, int smerLen,
@@ -233,7 +245,8 @@ uint64_t launch_extract_filter(const uint8_t* seq1, const uint64_t* off1, const 
                                unsigned long long* counter, uint64_t rankLo, uint64_t rankHi, uint64_t* emitted,
                                uint64_t cap, bool threadMajor, hipStream_t s,
                                uint8_t* qdig = nullptr, unsigned long long* binCnt = nullptr, uint64_t binRc = 0,
-                               uint64_t* binHost = nullptr, uint32_t upr = 0, const uint64_t* link = nullptr);
+                               uint64_t* binHost = nullptr, uint32_t upr = 0, const uint64_t* link = nullptr,
+                               bool seqFits = true);
 uint64_t launch_filter(const uint64_t* keys, uint64_t R, const ProbeLine* lines, uint64_t* qkey, uint32_t* qslot,
                        uint64_t* qfrom, unsigned long long* counter, uint64_t rankLo, uint64_t rankHi,
                        uint64_t* emitted, hipStream_t s);

@@ -219,6 +219,62 @@ def test_start_classify_tsv(make_db, tmp_path):
 
 
 @pytest.mark.gpu
+def test_start_classify_long_mate_beside_empty_mate(make_db, tmp_path):
+    """A paired FASTQ that holds pairs of a 5-kb mate and a mate below one window (5000/15, 15/5000): the
+    empty rule drops such a pair, so its batch keeps uniform units while one mate is far longer than the
+    217 bases a uniform batch's windows allow. The run classifies every read and the TSV is the oracle's,
+    line by line."""
+    from tests.test_batch_shapes import _genome_pair, covered
+    db_dir, taxo, gen = make_db("fmt2")
+    r = synth.make_reads(gen, 200, paired=True, seed=43)
+    m1, m2 = _mates(r, 1), _mates(r, 2)
+    # reads 70 and 150 fall in full 64-read batches (the first five ramp up: 2, 4, 8, 16, 32 reads), read 0 in
+    # the first, of two reads
+    odd = {0: (5000, 15), 70: (5000, 15), 150: (15, 5000)}
+    for i, (l1, l2) in odd.items():
+        a, b = _genome_pair(gen, i, l1, l2)
+        m1[i], m2[i] = bytes(a), bytes(b)
+    off = lambda ms: np.concatenate([[0], np.cumsum([len(m) for m in ms])]).astype(np.uint64)
+    r = synth.Reads(np.frombuffer(b"".join(m1), np.uint8).copy(), off(m1), np.frombuffer(b"".join(m2), np.uint8).copy(),
+                    off(m2), r.origin)
+    names = [f"p{i}" for i in range(r.n)]
+    p1, p2 = str(tmp_path / "p1.fq"), str(tmp_path / "p2.fq")
+    _write_fastq(p1, names, m1)
+    _write_fastq(p2, names, m2)
+    par = LocalParameters(seqMode=2, filenames=[p1, p2, db_dir])
+    par.load_db_parameters(db_dir)
+    out = str(tmp_path / "out.tsv")
+    with Classifier(par, db_dir=db_dir) as clf:
+        assert clf.startClassify(out, reads_per_batch=64) == r.n
+        assert clf.last_run["reads"] == r.n and clf.last_run["batches"] >= 4
+    odb = oc.OracleDb(db_dir)
+    ores, otc = oc.classify(odb, par.to_c(), r)
+    odb.close()
+    assert ores["is_classified"].sum() > 150
+    for i, (l1, l2) in odd.items():
+        assert not ores["is_classified"][i] and int(ores["query_length"][i]) == covered(l1) + covered(l2) == 5010
+    rank_of = dict(zip(taxo.taxid.tolist(), taxo.rank))
+    lines = open(out).read().split("\n")
+    assert lines[0] == "#is_classified\tname\ttaxID\tquery_length\tscore\trank\ttaxID:match_count"
+    body = [l for l in lines[1:] if l]
+    assert len(body) == r.n
+    for i, line in enumerate(body):
+        f = line.split("\t")
+        o = ores[i]
+        assert f[0] == ("1" if o["is_classified"] else "0") and f[1] == names[i]
+        assert int(f[2]) == (int(o["classification"]) if o["is_classified"] else 0)
+        assert int(f[3]) == int(o["query_length"])
+        assert f[4] == "%g" % float(o["score"])
+        if o["is_classified"]:
+            assert f[5] == rank_of.get(int(o["classification"]), "-")
+            s = int(o["taxcnt_offset"])
+            want = "".join(f"{int(t)}:{int(c)} " for t, c in otc[s:s + int(o["taxcnt_len"])])
+            assert f[6] == want
+        else:
+            assert f[5:] == ["-", "-", ""]
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["bgzf", "gzip"])
 def test_start_classify_long_reads_batches(make_db, tmp_path, mode):
     """A long-read (seq-mode 3) file larger than one batch: the pipeline cuts batches by bases
