@@ -430,13 +430,6 @@ static int open_into(mtb_ctx* c, HostDb& db, const mtb_params* par, int device, 
         c->rankHi = par->db_part == par->db_parts - 1 ? ~0ull : ((uint64_t)ends[1].hi << 32 | ends[1].lo) >> 24;
     }
     c->openS[1] = since(tp) - (c->openS[0] - readS);  // the decode's uploads are in openS[0]
-    set_ab_rank_free(getenv("MTB_AB_RANK_FREE") ? atoi(getenv("MTB_AB_RANK_FREE")) : 0);  // A/B only: invalid results
-    set_match_prefetch(getenv("MTB_MATCH_PREFETCH") ? atoi(getenv("MTB_MATCH_PREFETCH")) : 0);
-    set_pair_read(getenv("MTB_PAIR_READ") ? atoi(getenv("MTB_PAIR_READ")) : 0);
-    set_match_xcd(getenv("MTB_MATCH_XCD") ? atoi(getenv("MTB_MATCH_XCD")) : 0);  // (device-wide: set at each open)
-    // run sharing measured no gain (the repeated lookups already hit the L2: profiles/r05/ab_share*.json): off
-    set_share_runs(getenv("MTB_SHARE_RUNS") ? atoi(getenv("MTB_SHARE_RUNS")) : 0);
-    if (const char* e = getenv("MTB_AB_SWEEP_COUNT")) set_ab_sweep_count(atoi(e));  // A/B only: invalid results
     if (const char* e = getenv("MTB_MATCH_WINDOW")) c->matchWinCap = (uint32_t)strtoul(e, nullptr, 10);
     if (const char* e = getenv("MTB_FORCE_GENERIC")) c->forceGeneric = atoi(e) != 0;
     if (const char* e = getenv("MTB_SORT_LO_FINE")) {  // experiments: the unstaged join's sort prefix

@@ -1580,9 +1580,7 @@ static hipError_t launch_sorts(const mtb_match* in, const uint64_t* mOff, uint32
                                uint32_t inC, int mode, uint32_t* lists) {
     k_segsort_small<<<nReads, 64, 0, s>>>(in, mOff, seg, inOff, inC, nReads, out, liveCnt, pm, segLen);
     if (maxSeg <= 128) return hipGetLastError();
-    // MTB_SIZE_LISTS=0 (A/B): every bigger sort kernel over the whole batch, as before round 4
-    static const bool useLists = !(getenv("MTB_SIZE_LISTS") && atoi(getenv("MTB_SIZE_LISTS")) == 0);
-    if (!useLists || !lists) {
+    if (!lists) {  // every bigger sort kernel over the whole batch
 #define MTB_REGS(E, M) k_segsort_regs<E, M><<<nReads, 64, 0, s>>>(in, mOff, seg, inOff, inC, nReads, out, liveCnt, pm, segLen, nullptr)
         if (!liveCnt) mode = 3;
         if (maxSeg > 128) {
@@ -1625,10 +1623,8 @@ static hipError_t launch_sorts(const mtb_match* in, const uint64_t* mOff, uint32
     const uint32_t* listLarge = lists + 3 * (size_t)nReads;
     // mode (MTB_PRUNE_AFTER, A/B): segsort_regs' kMode of the E 4 and E 8 register sorts (4: as 2, with
     // the compact large sort on the plain bitonic network)
-    // MTB_SEGSORT_PAD=<bytes> (A/B diagnostic): unused dynamic LDS per block, to cap the waves per SIMD
-    static const size_t segPad = getenv("MTB_SEGSORT_PAD") ? (size_t)atoi(getenv("MTB_SEGSORT_PAD")) : 0;
 #define MTB_REGS(E, M, N, L) \
-    k_segsort_regs<E, M><<<N, 64, segPad, s>>>(in, mOff, seg, inOff, inC, nReads, out, liveCnt, pm, segLen, L)
+    k_segsort_regs<E, M><<<N, 64, 0, s>>>(in, mOff, seg, inOff, inC, nReads, out, liveCnt, pm, segLen, L)
     if (!liveCnt) mode = 3;  // no pruning: the full-key sort
     if (e == hipSuccess && cnt[0]) {
         if (mode == 1) MTB_REGS(4, 1, cnt[0], list4);
@@ -2145,7 +2141,7 @@ __device__ __forceinline__ void match_paths_group(const R& recs, const mtb_match
 // kPathStage matches.
 constexpr int kPathStage = 1024;
 
-// kLds = false (MTB_PATHS_NOLDS=1, A/B): no stage at all — at GTDB scale a wave's span of groups
+// kLds = false (MTB_PATHS_NOLDS=4, A/B and tests): no stage at all — at GTDB scale a wave's span of groups
 // rarely fits one (~2,200 matches) — so neither the 10-KB stage nor the register budget holds the
 // kernel at 4 waves per SIMD (kW: the waves the registers are held to)
 // kLook false (MTB_K6_LOOKAHEAD=0, A/B and tests): the unstaged groups' records by indexed reads
@@ -3219,9 +3215,9 @@ void launch_assign(const mtb_match* matches, const uint64_t* mOff, const uint32_
                 // groups of >= kBigGroup matches queue for a wave each (long reads' serial tail)
                 const bool waves = !a.generic && a.bigGroups && nM >= kBigGroup;
                 if (waves) hipMemsetAsync(s.waveCount, 0, sizeof(uint32_t), st);
-                // MTB_PATHS_NOLDS=<waves> (A/B, read per batch): the unstaged form held to 5 or 6 waves
+                // MTB_PATHS_NOLDS=4 (A/B and tests, read per batch): the unstaged form, held to 4 waves
                 const char* nl = getenv("MTB_PATHS_NOLDS");
-                const int nlw = nl ? atoi(nl) : 0;
+                const bool noLds = nl && atoi(nl) == 4;
                 // MTB_K6_LOOKAHEAD=0 (A/B and tests, read per batch): the path DP's records by indexed reads
                 const char* la = getenv("MTB_K6_LOOKAHEAD");
                 const bool look = !la || atoi(la) != 0;
@@ -3229,10 +3225,8 @@ void launch_assign(const mtb_match* matches, const uint64_t* mOff, const uint32_
     k_match_paths<L, W, A><<<(unsigned)((heavy + 63) / 64), 64, 0, st>>>(                                              \
         matches, s.gStart, inB ? s.ordKB : s.ordKA, heavy, cfg, tv, (Path*)s.local, (Path*)s.paths, s.conn,         \
         s.pathCnt, waves ? s.waveList : nullptr, s.waveCount)
-                if (nlw == 6) MTB_PATHS(false, 6, false);
-                else if (nlw == 5) MTB_PATHS(false, 5, false);
-                else if (nlw == 4 && look) MTB_PATHS(false, 4, true);
-                else if (nlw == 4) MTB_PATHS(false, 4, false);
+                if (noLds && look) MTB_PATHS(false, 4, true);
+                else if (noLds) MTB_PATHS(false, 4, false);
                 else if (look) MTB_PATHS(true, 1, true);
                 else MTB_PATHS(true, 1, false);
 #undef MTB_PATHS

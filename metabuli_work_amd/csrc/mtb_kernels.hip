@@ -1693,54 +1693,6 @@ __device__ __forceinline__ uint32_t wave_long_run(uint64_t key, uint32_t slot, u
     return c;
 }
 
-// The join in one pass. Each block selects its queries' candidates, counts them (per read with
-// atomics, per thread for the block), claims one contiguous stretch of the staging buffer with a
-// single atomic, and writes its matches there with the lanes' stretches adjacent. The buffer is
-// kStageRegions regions of `region` slots, each with its own counter (block b uses b mod
-// kStageRegions), so the claims do not all queue on one address. A later pass moves each match
-// into its read's segment (k_match_transpose). A region that would overflow is not written; the
-// caller grows the regions to the largest count and reruns.
-// A/B only (MTB_AB_RANK_FREE): k_match takes a query's rank in its read's segment
-// without the readCnt atomic (a wrong rank: the results are invalid), bounding what any scheme
-// that removes the atomic could save in the join; 2: nor the read's stretch bounds (dirOff).
-// Uniform units (round 6): 3 = no rank atomic (fixed lengths), 4 = nor the match writes.
-__device__ int g_abRankFree = 0;
-__device__ int g_matchXcd = 0;
-__device__ int g_shareRuns = 0;
-__device__ int g_pairRead = 0;
-// MTB_MATCH_PREFETCH=<m> (A/B, lean join): while a query's run-index entry is in flight, read the record
-// line its run most likely starts in — base + before + before * m / 256 (m ~ 256 * (records per
-// present rank - 1): 45 at GTDB scale) — so the dependent record read that follows hits the L2 when
-// the guess lands in the right line; 0: off
-__device__ int g_prefetch = 0;
-static int h_prefetch = 0;
-void set_match_prefetch(int m) {
-    h_prefetch = m;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prefetch), &m, sizeof(int));
-}
-
-static int h_pairRead = 0, h_matchXcd = 0, h_abRankFree = 0;  // host copies: k_join_uniform runs only without them
-void set_pair_read(int on) {
-    h_pairRead = on;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pairRead), &on, sizeof(int));
-}
-
-static int h_shareRuns = 0;  // host copy: the lean join (no sharing table) when off
-void set_share_runs(int on) {
-    h_shareRuns = on;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_shareRuns), &on, sizeof(int));
-}
-
-void set_match_xcd(int on) {
-    h_matchXcd = on;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_matchXcd), &on, sizeof(int));
-}
-
-void set_ab_rank_free(int on) {
-    h_abRankFree = on;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_abRankFree), &on, sizeof(int));
-}
-
 // The info of window p of uniform unit u (k_read_units: upr units per read, one per (mate, frame)), as
 // unit_windows + unit_info_at compute it: read u / upr, mate and frame from u % upr, the frame's first
 // window at its begin (KmerExtractor.cpp:374-378) plus the mate-2 offset (:341-345). L: the read's
@@ -1764,10 +1716,18 @@ __device__ __forceinline__ uint64_t uniform_unit_info(uint32_t u, uint32_t p, ui
     return unit_info_at(pack_info(r + 1, pos0 + posOffset, frame), p, kmerFormat);
 }
 
-// kLean: the unstaged join without the A/B options' LDS (run-length lines, run sharing): 18 KB of LDS
-// per block instead of 31, so LDS no longer caps the resident waves below what the VGPRs allow
-template <bool kStage, int kPer, int kLeanWaves = 0, bool kPrefetch = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanWaves ? kLeanWaves : 1))) k_match(const uint64_t* __restrict__ qkey, const uint32_t* __restrict__ qslot,
+// The join in one pass. Each block selects its queries' candidates, counts them (per read with
+// atomics, per thread for the block), claims one contiguous stretch of the staging buffer with a
+// single atomic, and writes its matches there with the lanes' stretches adjacent. The buffer is
+// kStageRegions regions of `region` slots, each with its own counter (block b uses b mod
+// kStageRegions), so the claims do not all queue on one address. A later pass moves each match
+// into its read's segment (k_match_transpose). A region that would overflow is not written; the
+// caller grows the regions to the largest count and reruns.
+// kStage: the block's DB window staged in LDS. kLean (unstaged only): no
+// run-length lines, so 18 KB of LDS per block instead of 27 and LDS no longer caps the resident waves
+// below what the VGPRs allow: held to 6 waves per SIMD (80 VGPRs, no spills).
+template <bool kStage, bool kLean>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLean ? 6 : 1))) k_match(const uint64_t* __restrict__ qkey, const uint32_t* __restrict__ qslot,
                                                const uint64_t* __restrict__ unitInfo, uint32_t C,
                                                uint64_t Q, const DbRec* __restrict__ db, uint64_t D, AADir d,
                                                const int32_t* __restrict__ spOf, uint32_t maxTax, int kmerFormat,
@@ -1782,7 +1742,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanW
                                                LongRun* __restrict__ longList, uint32_t longCap,
                                                uint32_t* __restrict__ longCnt, const ProbeExt* __restrict__ lineExt,
                                                uint32_t upr, unsigned long long* __restrict__ cnt64) {
-    constexpr bool kLean = kLeanWaves != 0;
+    static_assert(!(kStage && kLean), "the lean form is an unstaged one");
+    constexpr int kPer = kStage ? kMatchQ / 256 : kFreePer;
     // without staging (a DB much larger than the query stream: windows over the LDS cap) the
     // kernel holds no LDS window, so twice as many blocks fit on a CU to overlap the random reads
     __shared__ uint64_t sDb[kStage ? kMatchWin : 1];
@@ -1792,19 +1753,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanW
     ProbeLine* const sLines = reinterpret_cast<ProbeLine*>(sLineMem);
     const uint32_t* const sExt = reinterpret_cast<const uint32_t*>(sLineMem + (kStage ? 0 : kMatchLines * 4));
     __shared__ uint64_t sLineP[kStage ? 1 : kMatchLines];   // and their run-index bases
-    __shared__ unsigned long long sTbl[kStage || kLean ? 1 : 512];  // run sharing: (AA rank + 1) << 8 | leader
     __shared__ unsigned long long sBase;
-    static_assert(!kStage || kPer * 256 == kMatchQ, "staged blocks are the window blocks");
     const DbVal dbv{db};
     const DbTax dbtax{db};
-    // g_matchXcd (MTB_MATCH_XCD=1, A/B): the unstaged join's blocks remapped so each XCD takes one
-    // contiguous eighth of the sorted queries (neighbouring blocks' probe lines and records through one L2)
-    uint32_t blk = blockIdx.x;
-    if (!kStage && g_matchXcd) {
-        const uint32_t x = blockIdx.x & 7u, i = blockIdx.x >> 3, q = gridDim.x >> 3, r = gridDim.x & 7u;
-        blk = x * q + min(x, r) + i;
-    }
-    const uint64_t q0 = (uint64_t)blk * (256 * kPer);
+    const uint64_t q0 = (uint64_t)blockIdx.x * (256 * kPer);
     const uint64_t q1 = min(q0 + (uint64_t)(256 * kPer), Q);
     // every independent load of the block is issued up front (query keys and infos, the window
     // bounds, then the window) so their latencies overlap instead of adding up
@@ -1821,39 +1773,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanW
     const uint64_t winLo = kStage ? win[2 * blockIdx.x] : 0, winN = kStage ? win[2 * blockIdx.x + 1] - winLo : 0;
     const bool staged = kStage && winN <= (uint64_t)winCap;
     uint64_t lo[kPer], hi[kPer];
-    uint32_t pfw = 0;      // MTB_MATCH_PREFETCH's speculative reads (kept live below, never used)
     uint32_t nGallop = 0;  // probe-line queries whose run the run index does not hold (gallop fallback)
-    // Run sharing (the reference's same-AA reuse, KmerMatcher.cpp:315-353: a query whose AA part
-    // equals the previous one's reuses its candidates): the block's queries with the same AA rank —
-    // 13% of the queries of a uniform config-3 batch, 42% of a skewed-abundance one (MTB_DUP_STATS) —
-    // elect one leader through an LDS hash table; only the leader reads the run index and the run's
-    // first records, the followers take them from LDS. Each query still selects its own candidates.
-    // Measured (round 5, same box): no gain — uniform 55.7 -> 57.3 ms, skewed 54.4 -> 55.7 ms per batch:
-    // the repeated lookups hit the L2 already, and the barriers hold each block on its slowest leader.
-    // Off by default (MTB_SHARE_RUNS=1: on).
-    constexpr bool kShare = !kStage && kPer == 1 && !kLean;
-    const bool share = kShare && g_shareRuns && lines != nullptr;
-    bool follower = false;
-    uint32_t leadT = threadIdx.x;
-    if (share) {
-        for (uint32_t i = threadIdx.x; i < 512; i += 256) sTbl[i] = 0ull;
-        __syncthreads();
-        if (live[0]) {
-            const uint64_t rk = (key[0] & kAAMask) >> 24;
-            const unsigned long long want = ((rk + 1) << 8) | threadIdx.x;
-            uint32_t h = (uint32_t)((rk * 0x9E3779B97F4A7C15ull) >> 55);  // 9 bits
-            while (true) {
-                const unsigned long long old = atomicCAS(&sTbl[h], 0ull, want);
-                if (old == 0ull) break;  // the rank's leader
-                if ((old >> 8) == rk + 1) {
-                    follower = true;
-                    leadT = (uint32_t)(old & 255u);
-                    break;
-                }
-                h = (h + 1) & 511u;
-            }
-        }
-    }
     if (kStage && staged) {
         constexpr int kLoad = kMatchWin / 256;
         uint64_t v[kLoad];
@@ -1909,7 +1829,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanW
         for (int j = 0; j < kPer; j++) {
             const uint64_t aa = key[j] & kAAMask, x = aa >> 24, L = x / kLineRanks;
             const uint32_t o = (uint32_t)(x - L * kLineRanks);
-            if (!live[j] || follower) {  // a follower takes its leader's run below
+            if (!live[j]) {
                 lo[j] = hi[j] = 0;
                 continue;
             }
@@ -1931,14 +1851,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanW
                         continue;
                     }
                     const uint64_t p = (inLds ? sLineP[L - L0] : lineP[L]) + before;
-                    // both entries read unconditionally (p + 1 <= the index's end entry, allocated): no
-                    // branch between the loads and the prefetch's issue
+                    // both entries read unconditionally (p + 1 <= the index's end entry, allocated)
                     const uint32_t a = runOff[p], b1 = runOff[p + 1];
                     const uint32_t b = before + 1 < pc ? b1 : (uint32_t)cnt;
-                    if (kPrefetch) {  // after the run-index reads, unconditionally: waiting for them leaves it in flight
-                        const uint64_t gi = base + before + (((uint64_t)before * (uint32_t)g_prefetch) >> 8);
-                        pfw |= reinterpret_cast<const uint32_t*>(db)[3 * min(gi, D) + 2];
-                    }
                     lo[j] = base + a;
                     hi[j] = base + b;
                     continue;
@@ -1978,47 +1893,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanW
         if (hi[j] + vOff > D - 1) hi[j] = D - 1 - vOff;  // the last DB k-mer is never a candidate
         if (lo[j] > hi[j]) hi[j] = lo[j];
         small[j] = !staged && live[j] && hi[j] - lo[j] <= 2;
-        if (small[j] && !follower) {
+        if (small[j]) {
             // a random read moves a whole 128-B line (profiles/r05/random_fetch_calibration.json): the
-            // second record is read only for a two-record run (g_pairRead = 0, A/B: always, as before
-            // round 5), since it lies in the next line for ~1 in 10 records
-            const bool two = g_pairRead || hi[j] - lo[j] == 2;
+            // second record is read only for a two-record run, since it lies in the next line for ~1 in
+            // 10 records
+            const bool two = hi[j] - lo[j] == 2;
             const DbRec r0 = db[lo[j]], r1 = two ? db[lo[j] + 1] : DbRec{0, 0, 0};
             rv[j][0] = (uint64_t)r0.hi << 32 | r0.lo;
             rv[j][1] = (uint64_t)r1.hi << 32 | r1.lo;
             rt[j][0] = r0.tax;
             rt[j][1] = r1.tax;
-        }
-    }
-    if (kShare && share) {  // the leaders' runs to their followers, through the (now free) line stage
-        __syncthreads();    // every line scan of the block is done
-        uint64_t* sLo = reinterpret_cast<uint64_t*>(sLines);
-        uint64_t* sHi = sLo + 256;
-        uint64_t* sRv = sHi + 256;
-        uint32_t* sRt = reinterpret_cast<uint32_t*>(sRv + 512);
-        static_assert(kStage || (256 * 8 * 4 + 512 * 4) <= sizeof(uint4) * (kMatchLines + kExtLines) * 4, "results fit the line stage");
-        const uint32_t t = threadIdx.x;
-        if (!follower) {
-            sLo[t] = lo[0];
-            sHi[t] = hi[0];
-            if (small[0]) {
-                sRv[2 * t] = rv[0][0];
-                sRv[2 * t + 1] = rv[0][1];
-                sRt[2 * t] = rt[0][0];
-                sRt[2 * t + 1] = rt[0][1];
-            }
-        }
-        __syncthreads();
-        if (follower) {
-            lo[0] = sLo[leadT];
-            hi[0] = sHi[leadT];
-            small[0] = live[0] && hi[0] - lo[0] <= 2;
-            if (small[0]) {
-                rv[0][0] = sRv[2 * leadT];
-                rv[0][1] = sRv[2 * leadT + 1];
-                rt[0][0] = sRt[2 * leadT];
-                rt[0][1] = sRt[2 * leadT + 1];
-            }
         }
     }
     // long runs (direct join): scanned by the whole wave below, not by the lane
@@ -2027,7 +1911,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanW
     for (int j = 0; j < kPer; j++) longq[j] = longList && direct && !kStage && live[j] && hi[j] - lo[j] > kLongRun;
     uint32_t c[kPer], thr[kPer], rk[kPer], mine = 0;
     uint64_t stretch[kPer];
-    const int abFree = g_abRankFree;
     HamRows hr[kPer];
 #pragma unroll
     for (int j = 0; j < kPer; j++) {
@@ -2045,14 +1928,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanW
                    : staged ? run_select(hr[j], sDb, vOff, lo[j], hi[j], D, thr[j])
                             : run_select(hr[j], dbv, vOff, lo[j], hi[j], D, thr[j]);
         }
-        if (c[j] && upr && abFree >= 3) {  // A/B: the uniform path without its atomic (invalid results)
-            uint32_t p;
-            const uint32_t u = slot_unit(slot[j], C, p);
-            const uint32_t r = u / upr;
-            rk[j] = slot[j] & 7u;
-            info[j] = uniform_unit_info(u, p, upr, 150u | 150u << 16, kmerFormat);
-            stretch[j] = (uint64_t)r * upr | (uint64_t)upr << 40;
-        } else if (c[j] && upr && !abFree) {
+        if (c[j] && upr) {
             // uniform units: the read and the segment bounds from the slot; one 64-bit atomic on the
             // read's counter reserves the ranks (low word) and returns its mate lengths (high word)
             uint32_t p;
@@ -2068,7 +1944,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanW
             info[j] = unit_info_at(ur.x, p, kmerFormat);
             stretch[j] = ur.y;
             // the returned count is the query's first rank inside its read's segment
-            rk[j] = abFree ? (slot[j] & 7u) : atomicAdd(&readCnt[info_seq(info[j]) - 1], c[j]);
+            rk[j] = atomicAdd(&readCnt[info_seq(info[j]) - 1], c[j]);
         } else {
             info[j] = 0;
             stretch[j] = 0;
@@ -2089,7 +1965,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanW
             if (longq[j] && at < longCap) longList[at] = LongRun{q0 + threadIdx.x + (uint64_t)j * 256, lo[j], hi[j]};
         }
     }
-    if (kPrefetch && pfw == 0xFFFFFFFFu && key[0] == ~0ull) atomicAdd(&stats[kStatStripes], 0ull);  // keeps the prefetches
     const int blockHits = __syncthreads_count(hit >= 1) + (kPer > 1 ? __syncthreads_count(hit >= 2) : 0);
     // matched queries, on the block's stats stripe (one word for every block queued its atomics)
     if (threadIdx.x == 0 && blockHits) atomicAdd(&stats[blockIdx.x % kStatStripes], (unsigned long long)blockHits);
@@ -2107,9 +1982,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanW
         // bound sets the overflow flag and the caller reruns the batch with a larger one
 #pragma unroll
         for (int j = 0; j < kPer; j++) {
-            if (!c[j] || abFree == 4) continue;
-            const uint64_t o = abFree == 2 ? 0 : (stretch[j] & kStretchLoMask) * C;
-            const uint64_t cap = abFree == 2 ? (1u << 20) : ((stretch[j] >> 40) * C) >> capShift;
+            if (!c[j]) continue;
+            const uint64_t o = (stretch[j] & kStretchLoMask) * C;
+            const uint64_t cap = ((stretch[j] >> 40) * C) >> capShift;
             if (rk[j] + c[j] > cap) {
                 const uint64_t sp = atomicAdd(&total[0], (unsigned long long)c[j]);
                 if (sp + c[j] > region) {
@@ -2189,17 +2064,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLeanW
 // the run's two records, their taxa's species (read beside the rank atomic instead of after it)
 // and the query's Hamming rows: 50 VGPRs and 18.7 KB of LDS, so 8 waves per SIMD (the hardware's most;
 // k_match's lean form: 6). Same matches at the same ranks as k_match (KmerMatcher.cpp:360-448).
-// kMode 1 (round 6, default; MTB_JOIN_WAVE=0: kMode 0, the block form): each wave stages its own 64
-// queries' probe lines (≤ 16, one 16-B load per lane) and their run-index bases in a wave-private LDS
+// Each wave stages its own 64 queries' probe lines (≤ 16, one 16-B load per lane) and their run-index bases in a wave-private LDS
 // stretch, and tallies its matched queries with a lane-0 atomic on a stats stripe: no block barrier,
 // so the block's four waves run their dependent read chains (run index, records, rank atomic) out of
 // step with each other (join 47.4 -> 42.9 ms per 3.33M-pair batch, profiles/r06/ab_k4_wave.json).
-// kMode 2 / 3 (MTB_JOIN_WAVE=2 / 3, A/B: 7 / 6 waves per SIMD): resident waves walk their 64-query tiles with the next tile's probe
-// lines and the tile after's keys loaded while the current tile joins, so a tile's chain starts at
-// its run-index read.
+// kExt (the context holds run-length lines, MTB_LINE_EXT=1): they are staged beside the probe lines.
 constexpr int kWaveLines = 16;
-template <int kMode>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kMode == 2 ? 7 : (kMode == 3 ? 6 : 8))))
+template <bool kExt>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
 k_join_uniform(const uint64_t* __restrict__ qkey, const uint32_t* __restrict__ qslot, uint32_t C, uint64_t Q,
                const DbRec* __restrict__ db, uint64_t D, const int32_t* __restrict__ spOf, uint32_t maxTax,
                int kmerFormat, unsigned long long* __restrict__ total, mtb_match* __restrict__ buf,
@@ -2209,17 +2081,14 @@ k_join_uniform(const uint64_t* __restrict__ qkey, const uint32_t* __restrict__ q
                SegMatch* __restrict__ direct, int* __restrict__ overflow, uint32_t capShift,
                LongRun* __restrict__ longList, uint32_t longCap, uint32_t* __restrict__ longCnt, uint32_t upr,
                unsigned long long* __restrict__ cnt64, const ProbeExt* __restrict__ lineExt) {
-    constexpr bool kWave = kMode != 0;
-    constexpr bool kExt = kMode == 5;  // the wave form with run-length lines staged beside the probe lines
-    constexpr int kStageLines = kWave ? kWaveLines : kMatchLines;  // (per wave / per block)
-    __shared__ uint4 sLineMem[(kWave ? 4 : 1) * kStageLines * 4];
+    __shared__ uint4 sLineMem[4 * kWaveLines * 4];  // per wave
     __shared__ uint4 sExtMem[kExt ? 4 * kWaveLines * 4 : 1];
     uint4* const myExt4 = sExtMem + (kExt ? (threadIdx.x >> 6) * kWaveLines * 4 : 0);
     const uint32_t* const myExt = reinterpret_cast<const uint32_t*>(myExt4);
-    __shared__ uint64_t sLineP[(kWave ? 4 : 1) * kStageLines];
+    __shared__ uint64_t sLineP[4 * kWaveLines];
     const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
-    uint4* const myLines = sLineMem + (kWave ? wv * kStageLines * 4 : 0);
-    uint64_t* const myLineP = sLineP + (kWave ? wv * kStageLines : 0);
+    uint4* const myLines = sLineMem + wv * kWaveLines * 4;
+    uint64_t* const myLineP = sLineP + wv * kWaveLines;
     const ProbeLine* const sLines = reinterpret_cast<const ProbeLine*>(myLines);
     const DbVal dbv{db};
     const DbTax dbtax{db};
@@ -2311,13 +2180,8 @@ k_join_uniform(const uint64_t* __restrict__ qkey, const uint32_t* __restrict__ q
             at = (uint32_t)__shfl((int)at, 0, 64) + (uint32_t)__popcll(lm & ((1ull << lane) - 1));
             if (longq && live && at < longCap) longList[at] = LongRun{q, lo, hi};
         }
-        if (kMode != 0) {  // matched queries: a lane-0 atomic per wave on its stripe
-            const uint64_t hw = __ballot(c != 0);
-            if (lane == 0 && hw) atomicAdd(&stats[tile % kStatStripes], (unsigned long long)__popcll(hw));
-        } else {
-            const int blockHits = __syncthreads_count(c != 0);
-            if (threadIdx.x == 0 && blockHits) atomicAdd(&stats[blockIdx.x % kStatStripes], (unsigned long long)blockHits);
-        }
+        const uint64_t hw = __ballot(c != 0);  // matched queries: a lane-0 atomic per wave on its stripe
+        if (lane == 0 && hw) atomicAdd(&stats[tile % kStatStripes], (unsigned long long)__popcll(hw));
         const uint64_t gw = __ballot(gallop);
         if (gw && (threadIdx.x & 63) == 0) atomicAdd(&stats[kStatStripes], (unsigned long long)__popcll(gw));
         if (!c) return;
@@ -2366,343 +2230,35 @@ k_join_uniform(const uint64_t* __restrict__ qkey, const uint32_t* __restrict__ q
                      err);
         }
     };
-    if constexpr (kMode < 2 || kMode >= 5) {
-        // the wave's first query (kMode 1 runs with 256- or 64-thread blocks: MTB_JOIN_WAVE=4, A/B).
-        // kMode 7 (MTB_JOIN_WAVE=7, A/B): blocks dealt round-robin over the 8 XCDs walk contiguous
-        // eighths of the sorted queries, so neighbouring tiles share one L2
-        uint64_t blk = blockIdx.x;
-        if (kMode == 7) {
-            const uint64_t x = blk & 7u, i = blk >> 3, qn = gridDim.x >> 3, rn = gridDim.x & 7u;
-            blk = x * qn + min(x, rn) + i;
-        }
-        const uint64_t waveId = (blk * blockDim.x + threadIdx.x) >> 6;
-        const uint64_t q0 = kWave ? waveId * 64 : (uint64_t)blockIdx.x * 256;
-        if (kWave && q0 >= Q) return;  // a wave past the queries (no block barrier below in this form)
-        const uint64_t q1 = min(q0 + (kWave ? 64 : 256), Q);
-        const uint64_t q = q0 + (kWave ? (uint64_t)lane : threadIdx.x);
-        const bool live = q < q1;
-        const uint64_t key = live ? qkey[q] : 0;
-        const uint32_t slot = live ? qslot[q] : 0;
-        // the block's (wave's) probe lines (one contiguous stretch: sorted queries) and their run-index
-        // bases in LDS
-        uint64_t L0, L1;
-        lineSpan(kWave ? (uint64_t)__shfl((long long)key, 0, 64) : qkey[q0],
-                 kWave ? (uint64_t)__shfl((long long)key, (int)(q1 - q0 - 1), 64) : qkey[q1 - 1], L0, L1);
-        const bool inLds = L1 - L0 < (uint64_t)kStageLines;
-        if (inLds) {
-            const uint32_t nv = (uint32_t)(L1 - L0 + 1) * 4;
-            const uint4* src = reinterpret_cast<const uint4*>(lines + L0);
-            if (kWave) {  // one 16-B load per lane and a base per line, both in flight together
-                uint4 v{0, 0, 0, 0}, xv{0, 0, 0, 0};
-                uint64_t lp = 0;
-                if ((uint32_t)lane < nv) v = src[lane];
-                if (kExt && (uint32_t)lane < nv) xv = reinterpret_cast<const uint4*>(lineExt + L0)[lane];
-                if ((uint32_t)lane <= (uint32_t)(L1 - L0)) lp = lineP[L0 + lane];
-                if ((uint32_t)lane < nv) myLines[lane] = v;
-                if (kExt && (uint32_t)lane < nv) myExt4[lane] = xv;
-                if ((uint32_t)lane <= (uint32_t)(L1 - L0)) myLineP[lane] = lp;
-                // the wave's LDS writes complete in program order before any lane reads them back
-                __builtin_amdgcn_s_waitcnt(0);
-                __builtin_amdgcn_wave_barrier();
-            } else {
-                for (uint32_t i = threadIdx.x; i < nv; i += 256) myLines[i] = src[i];
-                for (uint32_t i = threadIdx.x; i <= (uint32_t)(L1 - L0); i += 256) myLineP[i] = lineP[L0 + i];
-                __syncthreads();
-            }
-        }
-        join(q, live, key, slot, L0, inLds, (uint32_t)waveId);
-    } else {
-        // resident waves: tile t = 64 sorted queries; wave w takes tiles w, w + W, w + 2W, ...
-        const uint64_t nT = (Q + 63) / 64, W = (uint64_t)gridDim.x * 4;
-        uint64_t t = (uint64_t)blockIdx.x * 4 + (uint64_t)wv;
-        if (t >= nT) return;
-        auto tileKeys = [&](uint64_t tt, uint64_t& k) {
-            const uint64_t qq = tt * 64 + (uint64_t)lane;
-            k = (tt < nT && qq < Q) ? qkey[qq] : 0;
-        };
-        auto tileSpan = [&](uint64_t tt, uint64_t k, uint64_t& L0, uint64_t& L1) {
-            const uint64_t qa = tt * 64, qb = min(qa + 64, Q);
-            lineSpan((uint64_t)__shfl((long long)k, 0, 64), (uint64_t)__shfl((long long)k, (int)(qb - qa - 1), 64), L0,
-                     L1);
-        };
-        auto stageLoad = [&](uint64_t L0, uint64_t L1, uint4& v, uint64_t& lp) {
-            v = uint4{0, 0, 0, 0};
-            lp = 0;
-            if (L1 - L0 < (uint64_t)kWaveLines) {
-                if ((uint32_t)lane < (uint32_t)(L1 - L0 + 1) * 4) v = reinterpret_cast<const uint4*>(lines + L0)[lane];
-                if ((uint32_t)lane <= (uint32_t)(L1 - L0)) lp = lineP[L0 + lane];
-            }
-        };
-        auto stageStore = [&](uint64_t L0, uint64_t L1, const uint4& v, uint64_t lp) {
-            if (L1 - L0 < (uint64_t)kWaveLines) {
-                if ((uint32_t)lane < (uint32_t)(L1 - L0 + 1) * 4) myLines[lane] = v;
-                if ((uint32_t)lane <= (uint32_t)(L1 - L0)) myLineP[lane] = lp;
-            }
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the LDS writes done; loads stay in flight
-            __builtin_amdgcn_wave_barrier();
-        };
-        uint64_t kc, kn, L0c, L1c;
-        tileKeys(t, kc);
-        tileKeys(t + W, kn);
-        tileSpan(t, kc, L0c, L1c);
-        {
-            uint4 v;
-            uint64_t lp;
-            stageLoad(L0c, L1c, v, lp);
-            stageStore(L0c, L1c, v, lp);
-        }
-        for (;;) {
-            const bool more = t + W < nT;
-            uint64_t L0n = 0, L1n = 0, kk;
-            uint4 v{0, 0, 0, 0};
-            uint64_t lp = 0;
-            if (more) {  // the next tile's probe lines in flight (its keys arrived during the last tile)
-                tileSpan(t + W, kn, L0n, L1n);
-                stageLoad(L0n, L1n, v, lp);
-            }
-            tileKeys(t + 2 * W, kk);  // the keys of the tile after it
-            const uint64_t q = t * 64 + (uint64_t)lane;
-            const uint32_t sc = q < Q ? qslot[q] : 0;  // needed at the rank atomic: in flight with the run index
-            join(q, q < Q, kc, sc, L0c, L1c - L0c < (uint64_t)kWaveLines, (uint32_t)t);
-            if (!more) break;
-            stageStore(L0n, L1n, v, lp);
-            t += W;
-            kc = kn;
-            kn = kk;
-            L0c = L0n;
-            L1c = L1n;
-        }
-    }
-}
-
-// k_join_uniform's wave form with two queries per lane (MTB_JOIN_WAVE=6, A/B): a wave takes 128 sorted
-// queries (lane l: queries l and l + 64) and stages their ≤ 32 probe lines; each phase of the chain
-// (run index, records, rank atomic) issues both queries' requests before waiting, so a SIMD keeps two
-// chains in flight per lane. K4 is bound by the chains in flight (8 / 6 / 4 waves per SIMD: 41.6 /
-// 46-49.5 / 56 ms per batch, profiles/r06/ab_k4_occ.json). Same matches at the same ranks.
-constexpr int kPairLines = 32;
-template <int kW>  // waves per SIMD the registers are held to (MTB_JOIN_WAVE=6 / 7 / 8)
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kW)))
-k_join_pair(const uint64_t* __restrict__ qkey, const uint32_t* __restrict__ qslot, uint32_t C, uint64_t Q,
-            const DbRec* __restrict__ db, uint64_t D, const int32_t* __restrict__ spOf, uint32_t maxTax,
-            int kmerFormat, unsigned long long* __restrict__ total, mtb_match* __restrict__ buf,
-            uint32_t* __restrict__ bufRank, uint64_t region, int* __restrict__ err,
-            const ProbeLine* __restrict__ lines, const uint64_t* __restrict__ lineP,
-            const uint16_t* __restrict__ runOff, int sortLo, unsigned long long* __restrict__ stats,
-            SegMatch* __restrict__ direct, int* __restrict__ overflow, uint32_t capShift,
-            LongRun* __restrict__ longList, uint32_t longCap, uint32_t* __restrict__ longCnt, uint32_t upr,
-            unsigned long long* __restrict__ cnt64) {
-    __shared__ uint4 sLineMem[4 * kPairLines * 4];
-    __shared__ uint64_t sLineP[4 * kPairLines];
-    const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
-    uint4* const myLines = sLineMem + wv * kPairLines * 4;
-    uint64_t* const myLineP = sLineP + wv * kPairLines;
-    const ProbeLine* const sLines = reinterpret_cast<const ProbeLine*>(myLines);
-    const DbVal dbv{db};
-    const DbTax dbtax{db};
-    const uint64_t waveId = (uint64_t)blockIdx.x * 4 + (uint64_t)wv;
-    const uint64_t q0 = waveId * 128;
-    if (q0 >= Q) return;
-    const uint64_t q1 = min(q0 + 128, Q);
-    uint64_t q[2], key[2];
-    uint32_t slot[2];
-    bool live[2];
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        q[j] = q0 + (uint64_t)(64 * j + lane);
-        live[j] = q[j] < q1;
-        key[j] = live[j] ? qkey[q[j]] : 0;
-        slot[j] = live[j] ? qslot[q[j]] : 0;
-    }
-    const int sh = sortLo - 24;
-    const int last = (int)(q1 - q0 - 1);
-    const uint64_t kFirst = (uint64_t)__shfl((long long)key[0], 0, 64);
-    const uint64_t kLast = (uint64_t)(last < 64 ? __shfl((long long)key[0], last, 64) : __shfl((long long)key[1], last - 64, 64));
-    const uint64_t L0 = ((kFirst >> sortLo) << sh) / kLineRanks;
-    const uint64_t L1 = ((((kLast >> sortLo) + 1) << sh) - 1) / kLineRanks;
-    const bool inLds = L1 - L0 < (uint64_t)kPairLines;
-    if (inLds) {  // two 16-B loads per lane and a base per line, all in flight together
+    // the wave's 64 queries
+    const uint64_t waveId = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t q0 = waveId * 64;
+    if (q0 >= Q) return;  // a wave past the queries (no block barrier below)
+    const uint64_t q1 = min(q0 + 64, Q);
+    const uint64_t q = q0 + (uint64_t)lane;
+    const bool live = q < q1;
+    const uint64_t key = live ? qkey[q] : 0;
+    const uint32_t slot = live ? qslot[q] : 0;
+    // the wave's probe lines (one contiguous stretch: sorted queries) and their run-index bases in LDS
+    uint64_t L0, L1;
+    lineSpan((uint64_t)__shfl((long long)key, 0, 64), (uint64_t)__shfl((long long)key, (int)(q1 - q0 - 1), 64), L0, L1);
+    const bool inLds = L1 - L0 < (uint64_t)kWaveLines;
+    if (inLds) {  // one 16-B load per lane and a base per line, both in flight together
         const uint32_t nv = (uint32_t)(L1 - L0 + 1) * 4;
         const uint4* src = reinterpret_cast<const uint4*>(lines + L0);
-        uint4 v0{0, 0, 0, 0}, v1{0, 0, 0, 0};
+        uint4 v{0, 0, 0, 0}, xv{0, 0, 0, 0};
         uint64_t lp = 0;
-        if ((uint32_t)lane < nv) v0 = src[lane];
-        if ((uint32_t)lane + 64 < nv) v1 = src[lane + 64];
+        if ((uint32_t)lane < nv) v = src[lane];
+        if (kExt && (uint32_t)lane < nv) xv = reinterpret_cast<const uint4*>(lineExt + L0)[lane];
         if ((uint32_t)lane <= (uint32_t)(L1 - L0)) lp = lineP[L0 + lane];
-        if ((uint32_t)lane < nv) myLines[lane] = v0;
-        if ((uint32_t)lane + 64 < nv) myLines[lane + 64] = v1;
+        if ((uint32_t)lane < nv) myLines[lane] = v;
+        if (kExt && (uint32_t)lane < nv) myExt4[lane] = xv;
         if ((uint32_t)lane <= (uint32_t)(L1 - L0)) myLineP[lane] = lp;
+        // the wave's LDS writes complete in program order before any lane reads them back
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
     }
-    // the runs: line scans from LDS, then both run-index reads
-    uint64_t lo[2] = {0, 0}, hi[2] = {0, 0};
-    bool gallop[2] = {false, false};
-    uint64_t rp[2] = {0, 0}, rbase[2] = {0, 0};
-    uint32_t rcnt[2] = {0, 0}, rlast[2] = {0, 0};
-    bool needIdx[2] = {false, false};
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        if (!live[j]) continue;
-        const uint64_t aa = key[j] & kAAMask, x = aa >> 24, L = x / kLineRanks;
-        const uint32_t o = (uint32_t)(x - L * kLineRanks);
-        const ProbeLine* pl = inLds ? sLines + (L - L0) : lines + L;
-        uint32_t before, pc;
-        bool present;
-        const uint64_t head = line_scan(pl, o, before, pc, present);
-        const uint64_t base = head & ((1ull << 40) - 1), cnt = head >> 40;
-        if (cnt > kRunIdxMax) {  // a line the run index does not hold: gallop from its lower bound
-            gallop[j] = true;
-            lo[j] = gallop_lower1(dbv, base + before, aa);
-            hi[j] = gallop_lower1(dbv, lo[j], aa + (1ull << 24));
-        } else if (present) {
-            needIdx[j] = true;
-            rp[j] = (inLds ? myLineP[L - L0] : lineP[L]) + before;
-            rbase[j] = base;
-            rcnt[j] = (uint32_t)cnt;
-            rlast[j] = before + 1 < pc ? 0u : 1u;
-        } else {
-            lo[j] = hi[j] = base;
-        }
-    }
-    uint32_t ra[2] = {0, 0}, rb[2] = {0, 0};
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-        if (needIdx[j]) {
-            ra[j] = runOff[rp[j]];
-            rb[j] = runOff[rp[j] + 1];
-        }
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        if (needIdx[j]) {
-            lo[j] = rbase[j] + ra[j];
-            hi[j] = rbase[j] + (rlast[j] ? rcnt[j] : rb[j]);
-        }
-        if (live[j]) {
-            if (lo[j] > D) {  // an inconsistent run index or probe line (k_match's check)
-                atomicExch(err, kErrRunOutsideDb);
-                lo[j] = D;
-            }
-            if (hi[j] > D - 1) hi[j] = D - 1;  // the last DB k-mer is never a candidate
-            if (lo[j] > hi[j]) hi[j] = lo[j];
-        }
-    }
-    // the runs' records, both queries' in flight together
-    bool small[2], longq[2];
-    uint64_t v0[2] = {0, 0}, v1[2] = {0, 0};
-    uint32_t t0[2] = {0, 0}, t1[2] = {0, 0};
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const uint64_t n = hi[j] - lo[j];
-        longq[j] = live[j] && n > kLongRun;
-        small[j] = live[j] && n <= 2;
-        if (small[j] && n) {
-            const DbRec r0 = db[lo[j]], r1 = n == 2 ? db[lo[j] + 1] : DbRec{0, 0, 0};
-            v0[j] = (uint64_t)r0.hi << 32 | r0.lo;
-            v1[j] = (uint64_t)r1.hi << 32 | r1.lo;
-            t0[j] = r0.tax;
-            t1[j] = r1.tax;
-        }
-    }
-    uint32_t c[2] = {0, 0}, thr[2] = {0, 0}, s0[2] = {255, 255}, s1[2] = {255, 255};
-    int32_t sp0[2] = {0, 0}, sp1[2] = {0, 0};
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const HamRows hr = hamming_rows(key[j]);
-        const uint64_t n = hi[j] - lo[j];
-        if (small[j]) {
-            s0[j] = n > 0 ? hamming_sum_rows(hr, v0[j]) : 255u;
-            s1[j] = n > 1 ? hamming_sum_rows(hr, v1[j]) : 255u;
-            thr[j] = min(min(s0[j], s1[j]) * 2u, 7u);
-            c[j] = (uint32_t)(s0[j] <= thr[j]) + (uint32_t)(s1[j] <= thr[j]);
-        } else if (live[j] && !longq[j]) {
-            c[j] = run_select(hr, dbv, 0, lo[j], hi[j], D, thr[j]);
-        }
-        const bool e0 = small[j] && s0[j] <= thr[j], e1 = small[j] && s1[j] <= thr[j];
-        sp0[j] = e0 ? (t0[j] <= maxTax ? spOf[t0[j]] : 0) : 0;
-        sp1[j] = e1 ? (t1[j] <= maxTax ? spOf[t1[j]] : 0) : 0;
-    }
-    // both rank atomics in flight together
-    uint32_t rk[2] = {0, 0}, rr[2] = {0, 0};
-    uint64_t info[2] = {0, 0};
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-        if (c[j]) {
-            uint32_t p;
-            const uint32_t u = slot_unit(slot[j], C, p);
-            rr[j] = u / upr;
-            const unsigned long long old = atomicAdd(&cnt64[rr[j]], (unsigned long long)c[j]);
-            rk[j] = (uint32_t)old;
-            info[j] = uniform_unit_info(u, p, upr, (uint32_t)(old >> 32), kmerFormat);
-        }
-    uint32_t hits = 0, gal = 0;
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const uint64_t lm = __ballot(longq[j]);
-        if (lm) {  // the wave's long queries to the long-run list (one atomic per wave), for k_match_long
-            uint32_t at = 0;
-            if (lane == 0) at = atomicAdd(longCnt, (uint32_t)__popcll(lm));
-            at = (uint32_t)__shfl((int)at, 0, 64) + (uint32_t)__popcll(lm & ((1ull << lane) - 1));
-            if (longq[j] && at < longCap) longList[at] = LongRun{q[j], lo[j], hi[j]};
-        }
-        hits += (uint32_t)__popcll(__ballot(c[j] != 0));
-        gal += (uint32_t)__popcll(__ballot(gallop[j]));
-    }
-    if (lane == 0 && hits) atomicAdd(&stats[waveId % kStatStripes], (unsigned long long)hits);
-    if (lane == 0 && gal) atomicAdd(&stats[kStatStripes], (unsigned long long)gal);
-    const uint64_t cap = ((uint64_t)upr * C) >> capShift;
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        if (!c[j]) continue;
-        const bool rev = ((info_frame(info[j]) < 3) != (kmerFormat == 2));
-        // the read's stretch of upr units (C slots each) bounds its segment; ranks past it spill to buf
-        const bool spill = rk[j] + c[j] > cap;
-        uint64_t w = rk[j];
-        if (spill) {
-            const uint64_t sp = atomicAdd(&total[0], (unsigned long long)c[j]);
-            if (sp + c[j] > region) {
-                atomicExch(overflow, 1);
-                continue;
-            }
-            w = sp;
-        }
-        SegMatch* const out = direct + (uint64_t)rr[j] * upr * C;
-        if (small[j]) {
-            const HamRows hr = hamming_rows(key[j]);
-            uint32_t rkj = rk[j];
-#pragma unroll
-            for (int k = 0; k < 2; k++) {
-                if (!(k ? s1[j] <= thr[j] : s0[j] <= thr[j])) continue;
-                const uint64_t tv = k ? v1[j] : v0[j];
-                const uint32_t tax = k ? t1[j] : t0[j], hs = k ? s1[j] : s0[j];
-                const int32_t sp = k ? sp1[j] : sp0[j];
-                if (tax == 0 || sp <= 0) atomicExch(err, kErrTaxid);  // KmerMatcher.cpp:432-441 exits
-                mtb_match m;
-                m.qinfo = info[j];
-                m.target_id = tax;
-                m.species_id = (uint32_t)sp;
-                m.dna_encoding = (uint32_t)(tv & 0xFFFFFFull);
-                m.right_end_hamming = (uint16_t)hammings_rows(hr, key[j], tv, rev);
-                m.hamming = (uint8_t)hs;
-                m.pad = 0;
-                if (spill) {
-                    bufRank[w] = rkj++;
-                    buf[w] = m;
-                } else {
-                    out[w] = seg_pack(m);
-                }
-                w++;
-            }
-        } else {
-            const HamRows hr = hamming_rows(key[j]);
-            if (spill)
-                run_emit(key[j], hr, info[j], dbv, dbtax, lo[j], hi[j], thr[j], spOf, maxTax, kmerFormat, buf, bufRank, w,
-                         w + c[j], rk[j], err);
-            else
-                run_emit(key[j], hr, info[j], dbv, dbtax, lo[j], hi[j], thr[j], spOf, maxTax, kmerFormat, out,
-                         (uint32_t*)nullptr, w, w + c[j], 0, err);
-        }
-    }
+    join(q, live, key, slot, L0, inLds, (uint32_t)waveId);
 }
 
 // The long-run list of the direct join: one wave per long query (wave_long_run).
@@ -2849,22 +2405,21 @@ __global__ void __launch_bounds__(256) k_filter(const uint64_t* __restrict__ key
 // threads share the group loop up to the block's longest unit (a unit past its windows, or a padding
 // unit, contributes sentinels). The emitted-window count goes to the counter once per wave at the
 // end: same-address atomics are what the kernel waits on when it has no probes to make (round 4:
-// a per-wave-per-group counter atomic tripled the probe-free pass, `MTB_AB_FILTER=1`). Output: qkey /
-// qslot as k_filter's (slot = the window's K1 slot).
+// a per-wave-per-group counter atomic tripled the probe-free pass). Output: qkey / qslot as k_filter's
+// (slot = the window's K1 slot).
 constexpr uint32_t kBinStage = 2560;  // binned K1F: windows per group staged in LDS (a group keeps ~1.9k at GTDB scale)
-// kLink: window pairs through the link lines — 3: at the registers the code takes (3 waves per SIMD),
-// 4: held to 128 VGPRs (4 waves, a few spills); 0: one probe-line read per window. kSplit: the group's
-// probes issued after its scan instead of as each window's (pair's) key is known. kSeqLds (uniform units
-// only): the block's reads' bases staged in LDS first, so the scan loads nothing from HBM — a load's
-// wait counter drains in issue order, and a base load issued behind a probe waits for that probe
-// (kSeqStage bytes, mtb_launch.h: 23 read pairs or 44 single reads of at most kSeqMate bases; the launcher takes
-// this form only when no mate of the batch is longer)
-// kWavePack (MTB_K1F_WAVEPACK=1, A/B): each wave packs its own present windows with its own counter
-// atomic per group — no block barrier per group (the K4 finding: a block's waves held at a barrier
-// wait for its slowest lane's random reads)
-template <int kPer, bool kJMajor, bool kBinned = false, int kLink = 0, bool kSplit = false, bool kSeqLds = false,
-          bool kWavePack = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLink == 4 ? 4 : 1))) k_extract_filter(const uint8_t* __restrict__ seq1, const uint64_t* __restrict__ off1,
+// kLink: window pairs through the link lines, held to 128 VGPRs (4 waves per SIMD, a few spills), each
+// pair's probes issued as its keys are known; else one probe-line read per window, and the packed forms
+// issue a group's probes together after its scan (the binned form as each key is known). kSeqLds (link
+// lines, uniform units only): the block's reads' bases staged in LDS first, so the scan loads nothing
+// from HBM — a load's wait counter drains in issue order, and a base load issued behind a probe waits
+// for that probe (kSeqStage bytes, mtb_launch.h: 23 read pairs or 44 single reads of at most kSeqMate
+// bases; the launcher takes this form only when no mate of the batch is longer)
+// kWavePack (MTB_K1F_WAVEPACK=1, A/B; link lines with the LDS stage only): each wave packs its own
+// present windows with its own counter atomic per group — no block barrier per group (the K4 finding: a
+// block's waves held at a barrier wait for its slowest lane's random reads)
+template <bool kJMajor, bool kBinned, bool kLink, bool kSeqLds, bool kWavePack = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLink ? 4 : 1))) k_extract_filter(const uint8_t* __restrict__ seq1, const uint64_t* __restrict__ off1,
                                                         const uint8_t* __restrict__ seq2, const uint64_t* __restrict__ off2,
                                                         const ReadMeta* __restrict__ meta, const uint64_t* __restrict__ uOff,
                                                         const uint32_t* __restrict__ unitRead, uint64_t nUnits, uint32_t C,
@@ -2874,9 +2429,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLink 
                                                         unsigned long long* __restrict__ counter, uint64_t rankLo,
                                                         uint64_t rankHi, uint64_t cap, uint8_t* __restrict__ qdig,
                                                         unsigned long long* __restrict__ binCnt, uint64_t binRc,
-                                                        uint32_t upr, const uint64_t* __restrict__ link,
-                                                        int emitPerBlock = 0) {
-    static_assert(kLink == 0 || kPer % 2 == 0, "windows probed in pairs");
+                                                        uint32_t upr, const uint64_t* __restrict__ link) {
+    constexpr int kPer = kFilterPer;
+    constexpr bool kSplit = !kLink && !kBinned;
+    static_assert(kPer % 2 == 0, "windows probed in pairs");
+    static_assert(!kSeqLds || kLink, "the LDS stage goes with the link lines");
+    static_assert(!kWavePack || kSeqLds, "per-wave packing exists for the production form only");
+    constexpr bool kEmitPerBlock = kSeqLds && !kWavePack;
     __shared__ uint8_t sBase[256];
     __shared__ uint32_t sBin[256];
     __shared__ uint32_t sBinBase[256];
@@ -3141,12 +2700,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLink 
         }
     }
     // the reference's "Query k-mer number" (KmerMatcher.cpp:143-152) counts every non-blank query
-    // k-mer, before any AA test: one atomic per wave, or (emitPerBlock, the default for the production
-    // form) per block — the count shares its line with the output counter the groups' atomics wait on,
-    // and same-line atomics are served one at a time
+    // k-mer, before any AA test: one atomic per wave, or (kEmitPerBlock, the production form) per block — the
+    // count shares its line with the output counter the groups' atomics wait on, and same-line atomics
+    // are served one at a time
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) emitted += (uint32_t)__shfl_xor((int)emitted, d, 64);
-    if (emitPerBlock) {
+    if constexpr (kEmitPerBlock) {
         __shared__ uint32_t sEmit[kWaves];
         if ((threadIdx.x & 63) == 0) sEmit[wv] = emitted;
         __syncthreads();
@@ -3156,9 +2715,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLink 
             for (int i = 0; i < kWaves; i++) e += sEmit[i];
             if (e) atomicAdd(counter + 1, (unsigned long long)e);
         }
-        return;
+    } else {
+        if ((threadIdx.x & 63) == 0 && emitted) atomicAdd(counter + 1, (unsigned long long)emitted);
     }
-    if ((threadIdx.x & 63) == 0 && emitted) atomicAdd(counter + 1, (unsigned long long)emitted);
 }
 
 uint64_t launch_extract_filter(const uint8_t* seq1, const uint64_t* off1, const uint8_t* seq2, const uint64_t* off2,
@@ -3177,64 +2736,28 @@ uint64_t launch_extract_filter(const uint8_t* seq1, const uint64_t* off1, const 
     hipMemsetAsync(counter, 0, 2 * sizeof(unsigned long long), s);
     if (nUnits) {
         const uint64_t threads = (nUnits + 63) / 64 * 64;
-        // MTB_FILTER_PER (A/B): windows per probe group (16: the default; 8: fewer registers, more waves)
-        static const int per = getenv("MTB_FILTER_PER") && atoi(getenv("MTB_FILTER_PER")) == 8 ? 8 : 16;
-        const bool jMajor = !threadMajor;
         const unsigned blocks = (unsigned)((threads + 255) / 256);
         const size_t lds = binRc ? kBinStage * (sizeof(uint64_t) + sizeof(uint32_t)) : 0;
-#define MTB_EF(P, J)                                                                                                  \
-    k_extract_filter<P, J, false, 0, true><<<blocks, 256, lds, s>>>(seq1, off1, seq2, off2, meta, uOff, unitRead, nUnits, C, \
-                                                  extract_tables(t), kmerFormat, syncmer, smerLen, unitInfo, lines, qkey, \
-                                                  qslot, counter, rankLo, rankHi, cap, qdig, binCnt, binRc, upr, nullptr)
-        if (binRc) {
-            k_extract_filter<kFilterPer, true, true><<<blocks, 256, lds, s>>>(
-                seq1, off1, seq2, off2, meta, uOff, unitRead, nUnits, C, extract_tables(t), kmerFormat, syncmer, smerLen,
-                unitInfo, lines, qkey, qslot, counter, rankLo, rankHi, cap, qdig, binCnt, binRc, upr, nullptr);
-        } else if (link && jMajor) {  // window pairs through the link lines (the default when the context has them)
-            // MTB_LINK_FORM (A/B, read per batch): w<waves><s|i>[8] — 4 or 3 waves per SIMD, probes issued
-            // after the group's scan (s) or interleaved (i), groups of 8 windows instead of 16
-            const char* lf = getenv("MTB_LINK_FORM");
-            const std::string f = lf ? lf : "w4i";
-#define MTB_EFL(P, W, S)                                                                                            \
-    k_extract_filter<P, true, false, W, S><<<blocks, 256, lds, s>>>(                                                \
-        seq1, off1, seq2, off2, meta, uOff, unitRead, nUnits, C, extract_tables(t), kmerFormat, syncmer, smerLen,   \
-        unitInfo, lines, qkey, qslot, counter, rankLo, rankHi, cap, qdig, binCnt, binRc, upr, link)
-            // MTB_K1F_EMIT_BLOCK=0 (A/B, read per batch): the emitted count by one atomic per wave
-            const char* eb = getenv("MTB_K1F_EMIT_BLOCK");
-            const int emitBlock = !eb || atoi(eb) != 0;
-#define MTB_EFLS(P, W, S)                                                                                           \
-    k_extract_filter<P, true, false, W, S, true><<<blocks, 256, lds, s>>>(                                          \
-        seq1, off1, seq2, off2, meta, uOff, unitRead, nUnits, C, extract_tables(t), kmerFormat, syncmer, smerLen,   \
-        unitInfo, lines, qkey, qslot, counter, rankLo, rankHi, cap, qdig, binCnt, binRc, upr, link, emitBlock)
-            const char* wp = getenv("MTB_K1F_WAVEPACK");  // A/B, read per batch
-            const bool wavePack = wp && atoi(wp) != 0;
-            // the bases staged in LDS (uniform batches with no mate past kSeqMate bases; MTB_K1F_SEQ_LDS=0,
-            // A/B: read from HBM)
-            const char* sl = getenv("MTB_K1F_SEQ_LDS");
-            const bool seqLds = upr && seqFits && (!sl || atoi(sl) != 0);
-            if (seqLds && wavePack && f == "w4i")
-                k_extract_filter<16, true, false, 4, false, true, true><<<blocks, 256, lds, s>>>(
-                    seq1, off1, seq2, off2, meta, uOff, unitRead, nUnits, C, extract_tables(t), kmerFormat, syncmer,
-                    smerLen, unitInfo, lines, qkey, qslot, counter, rankLo, rankHi, cap, qdig, binCnt, binRc, upr, link);
-            else if (seqLds && f == "w3i") MTB_EFLS(16, 3, false);
-            else if (seqLds && f == "w3i8") MTB_EFLS(8, 3, false);
-            else if (seqLds) MTB_EFLS(16, 4, false);
-            else if (f == "w3i") MTB_EFL(16, 3, false);
-            else if (f == "w3s") MTB_EFL(16, 3, true);
-            else if (f == "w4s") MTB_EFL(16, 4, true);
-            else if (f == "w3i8") MTB_EFL(8, 3, false);
-            else if (f == "w3s8") MTB_EFL(8, 3, true);
-            else MTB_EFL(16, 4, false);
-#undef MTB_EFLS
-#undef MTB_EFL
-        } else if (per == 8) {
-            if (jMajor) MTB_EF(8, true);
-            else MTB_EF(8, false);
-        } else {
-            if (jMajor) MTB_EF(kFilterPer, true);
-            else MTB_EF(kFilterPer, false);
-        }
-#undef MTB_EF
+        // the link-line form stages its bases in LDS (uniform batches with no mate past kSeqMate bases;
+        // MTB_K1F_SEQ_LDS=0, A/B: read from HBM)
+        const char* sl = getenv("MTB_K1F_SEQ_LDS");
+        const bool seqLds = upr && seqFits && (!sl || atoi(sl) != 0);
+        const char* wp = getenv("MTB_K1F_WAVEPACK");  // A/B, read per batch
+        const bool wavePack = wp && atoi(wp) != 0;
+        const ExtractTables tabs = extract_tables(t);
+        // every form takes the same arguments (a form without link lines never reads `link`)
+        auto launch = [&](auto kernel) {
+            kernel<<<blocks, 256, lds, s>>>(seq1, off1, seq2, off2, meta, uOff, unitRead, nUnits, C, tabs, kmerFormat,
+                                            syncmer, smerLen, unitInfo, lines, qkey, qslot, counter, rankLo, rankHi, cap,
+                                            qdig, binCnt, binRc, upr, link);
+        };
+        const bool linked = link && !threadMajor;
+        if (binRc) launch(k_extract_filter<true, true, false, false>);
+        else if (linked && seqLds && wavePack) launch(k_extract_filter<true, false, true, true, true>);
+        else if (linked && seqLds) launch(k_extract_filter<true, false, true, true>);  // the default with link lines
+        else if (linked) launch(k_extract_filter<true, false, true, false>);
+        else if (!threadMajor) launch(k_extract_filter<true, false, false, false>);
+        else launch(k_extract_filter<false, false, false, false>);
     }
     unsigned long long Q[2] = {0, 0};
     hipMemcpyAsync(Q, counter, sizeof(Q), hipMemcpyDeviceToHost, s);
@@ -3250,41 +2773,6 @@ uint64_t launch_extract_filter(const uint8_t* seq1, const uint64_t* off1, const 
     if (binRc) {
         Q[0] = 0;
         for (int r = 0; r < kSortBins; r++) Q[0] += binHost[r];
-    }
-    // MTB_AB_FILTER=1 (diagnostics; results unaffected): after the real pass, two timed passes that
-    // write no output (cap 0) and count into a scratch word — with the probes, and with none (an empty
-    // rank range) — to split the kernel's time between the probe-line reads, the scan and the packing
-    static const bool abDiag = getenv("MTB_AB_FILTER") && atoi(getenv("MTB_AB_FILTER")) == 1;
-    if (abDiag && nUnits) {
-        const unsigned blocks = (unsigned)(((nUnits + 63) / 64 * 64 + 255) / 256);
-        unsigned long long* sc = nullptr;
-        hipEvent_t ev[3];
-        if (hipMalloc((void**)&sc, 2 * sizeof(unsigned long long)) == hipSuccess) {
-            for (auto& e : ev) hipEventCreate(&e);
-            hipMemsetAsync(sc, 0, 2 * sizeof(unsigned long long), s);
-            // the form the batch ran (link lines: without probes every window reads word 0, from the cache)
-            hipEventRecord(ev[0], s);
-            for (int pass = 0; pass < 2; pass++) {
-                const uint64_t lo = pass ? 0 : rankLo, hi = pass ? 0 : rankHi;
-                if (link)
-                    k_extract_filter<kFilterPer, true, false, 4><<<blocks, 256, 0, s>>>(
-                        seq1, off1, seq2, off2, meta, uOff, unitRead, nUnits, C, extract_tables(t), kmerFormat, syncmer,
-                        smerLen, unitInfo, lines, qkey, qslot, sc, lo, hi, 0, nullptr, nullptr, 0, upr, link);
-                else
-                    k_extract_filter<kFilterPer, true, false, 0, true><<<blocks, 256, 0, s>>>(
-                        seq1, off1, seq2, off2, meta, uOff, unitRead, nUnits, C, extract_tables(t), kmerFormat, syncmer,
-                        smerLen, unitInfo, lines, qkey, qslot, sc, lo, hi, 0, nullptr, nullptr, 0, upr, nullptr);
-                hipEventRecord(ev[pass + 1], s);
-            }
-            hipStreamSynchronize(s);
-            float a = 0, b = 0;
-            hipEventElapsedTime(&a, ev[0], ev[1]);
-            hipEventElapsedTime(&b, ev[1], ev[2]);
-            fprintf(stderr, "[mtb ab filter] windows %llu present %llu: probes, no output %.3f ms; no probes %.3f ms\n",
-                    (unsigned long long)Q[1], (unsigned long long)Q[0], a, b);
-            for (auto& e : ev) hipEventDestroy(e);
-            hipFree(sc);
-        }
     }
     return Q[0];
 }
@@ -3553,92 +3041,32 @@ void launch_match(const uint64_t* qkey, const uint32_t* qslot, const uint64_t* u
     // HBM path anyway
     if (unstaged_join(lines != nullptr, D, Q, winCap)) {
         const unsigned blocks = (unsigned)((Q + 256 * kFreePer - 1) / (256 * kFreePer));
-        // MTB_MATCH_LEAN=0 (A/B, read per batch): the full-LDS form even without run-length lines or sharing
-        const char* le = getenv("MTB_MATCH_LEAN");
-        const bool leanOk = !le || atoi(le) != 0;
-        // MTB_MATCH_WAVES (A/B, read per batch): the lean form's waves per SIMD — 6 (80 VGPRs, no
-        // spills; the default), 7 or 8 (72 / 64 VGPRs with scratch spills)
-        const char* we = getenv("MTB_MATCH_WAVES");
-        const int waves = we ? atoi(we) : 6;
-#define MTB_K4_LEAN(W)                                                                                             \
-    k_match<false, kFreePer, W, false><<<blocks, 256, 0, s>>>(qkey, qslot, unitInfo, C, Q, db, D, dir, spOf, maxTax, kmerFormat, \
-                                                       readCnt, total, buf, bufRank, region, err, winCap, win, lines,   \
-                                                       lineP, runOff, sortLo, stats, direct, dirOff, overflow, capShift, \
-                                                       longList, longCap, longCnt, nullptr, upr, cnt64)
-        // MTB_JOIN_FAST=0 (A/B, read per batch): the production configuration through k_match's lean form
-        // instead of k_join_uniform
+        // MTB_JOIN_FAST=0 (A/B, read per batch): the production configuration through k_match instead of
+        // k_join_uniform
         const char* fe = getenv("MTB_JOIN_FAST");
-        const char* wfe = getenv("MTB_JOIN_WAVE");  // run-length lines: only the wave form (mode 5) reads them
-        const bool fastOk = (!fe || atoi(fe) != 0) && leanOk && lines && runOff &&
-                            (!lineExt || !wfe || atoi(wfe) == 1) && direct && longList &&
-                            upr && cnt64 && !h_shareRuns && !h_prefetch && !h_pairRead && !h_matchXcd &&
-                            !h_abRankFree;
-        if (fastOk) {
-            // MTB_JOIN_WAVE=1 (A/B, read per batch): the per-wave staging form
-            const char* wf = getenv("MTB_JOIN_WAVE");
-            const int wmode = wf ? atoi(wf) : 1;
-            unsigned grid = (unsigned)((Q + 255) / 256);
-#define MTB_K4_JOIN(M)                                                                                              \
-    k_join_uniform<M><<<grid, 256, 0, s>>>(qkey, qslot, C, Q, db, D, spOf, maxTax, kmerFormat, total, buf, bufRank,  \
-                                           region, err, lines, lineP, runOff, sortLo, stats, direct, overflow,      \
-                                           capShift, longList, longCap, longCnt, upr, cnt64, lineExt)
-            if (wmode == 2 || wmode == 3) {  // resident waves: 7 (6) blocks of 4 waves per CU
-                int dev = 0, cus = 256;
-                if (hipGetDevice(&dev) == hipSuccess)
-                    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                grid = std::min<unsigned>(grid, (unsigned)std::max(cus, 1) * (wmode == 2 ? 7u : 6u));
-                if (wmode == 2) MTB_K4_JOIN(2);
-                else MTB_K4_JOIN(3);
-            } else if (wmode == 4) {  // a wave per block: a finished wave frees its slot at once
-                k_join_uniform<1><<<(unsigned)((Q + 63) / 64), 64, 0, s>>>(
-                    qkey, qslot, C, Q, db, D, spOf, maxTax, kmerFormat, total, buf, bufRank, region, err, lines, lineP,
-                    runOff, sortLo, stats, direct, overflow, capShift, longList, longCap, longCnt, upr, cnt64, nullptr);
-            } else if (lineExt) {  // MTB_LINE_EXT=1 with the wave form: runs from the staged run-length lines
-                MTB_K4_JOIN(5);
-            } else if (wmode >= 6 && wmode <= 8) {  // two queries per lane
-#define MTB_K4_PAIR(W)                                                                                              \
-    k_join_pair<W><<<(unsigned)((Q + 511) / 512), 256, 0, s>>>(qkey, qslot, C, Q, db, D, spOf, maxTax, kmerFormat,   \
-                                                              total, buf, bufRank, region, err, lines, lineP, runOff, \
-                                                              sortLo, stats, direct, overflow, capShift, longList,    \
-                                                              longCap, longCnt, upr, cnt64)
-                if (wmode == 6) MTB_K4_PAIR(6);
-                else if (wmode == 7) MTB_K4_PAIR(7);
-                else MTB_K4_PAIR(8);
-#undef MTB_K4_PAIR
-            } else if (wmode == 1 && getenv("MTB_JOIN_PAD")) {
-                // A/B diagnostic: dynamic LDS reserved per block (unused) to cap the waves per SIMD
-                k_join_uniform<1><<<grid, 256, (size_t)atoi(getenv("MTB_JOIN_PAD")), s>>>(
-                    qkey, qslot, C, Q, db, D, spOf, maxTax, kmerFormat, total, buf, bufRank, region, err, lines, lineP,
-                    runOff, sortLo, stats, direct, overflow, capShift, longList, longCap, longCnt, upr, cnt64, lineExt);
-            } else if (wmode == 7) {
-                MTB_K4_JOIN(7);
-            } else if (wmode == 1) {
-                MTB_K4_JOIN(1);
-            } else {
-                MTB_K4_JOIN(0);
-            }
-#undef MTB_K4_JOIN
-        } else
-        if (leanOk && !(runOff && lineExt) && !h_shareRuns && h_prefetch && runOff) {
-            k_match<false, kFreePer, 6, true><<<blocks, 256, 0, s>>>(qkey, qslot, unitInfo, C, Q, db, D, dir, spOf, maxTax,
-                                                                     kmerFormat, readCnt, total, buf, bufRank, region,
-                                                                     err, winCap, win, lines, lineP, runOff, sortLo,
-                                                                     stats, direct, dirOff, overflow, capShift, longList,
-                                                                     longCap, longCnt, nullptr, upr, cnt64);
-        } else if (leanOk && !(runOff && lineExt) && !h_shareRuns) {
-            if (waves == 8) MTB_K4_LEAN(8);
-            else if (waves == 7) MTB_K4_LEAN(7);
-            else MTB_K4_LEAN(6);
-        } else
-#undef MTB_K4_LEAN
-            k_match<false, kFreePer><<<blocks, 256, 0, s>>>(qkey, qslot, unitInfo, C, Q, db, D, dir, spOf, maxTax,
-                                                            kmerFormat, readCnt, total, buf, bufRank, region, err, winCap,
-                                                            win, lines, lineP, runOff, sortLo, stats, direct, dirOff,
-                                                            overflow, capShift, longList, longCap, longCnt,
-                                                            runOff ? lineExt : nullptr, upr, cnt64);
+        const bool fastOk = (!fe || atoi(fe) != 0) && lines && runOff && direct && longList && upr && cnt64;
+        const bool ext = runOff && lineExt;  // run-length lines (MTB_LINE_EXT=1) staged beside the probe lines
+        if (fastOk && ext)
+            k_join_uniform<true><<<(unsigned)((Q + 255) / 256), 256, 0, s>>>(
+                qkey, qslot, C, Q, db, D, spOf, maxTax, kmerFormat, total, buf, bufRank, region, err, lines, lineP, runOff,
+                sortLo, stats, direct, overflow, capShift, longList, longCap, longCnt, upr, cnt64, lineExt);
+        else if (fastOk)
+            k_join_uniform<false><<<(unsigned)((Q + 255) / 256), 256, 0, s>>>(
+                qkey, qslot, C, Q, db, D, spOf, maxTax, kmerFormat, total, buf, bufRank, region, err, lines, lineP, runOff,
+                sortLo, stats, direct, overflow, capShift, longList, longCap, longCnt, upr, cnt64, nullptr);
+        else if (ext)
+            k_match<false, false><<<blocks, 256, 0, s>>>(qkey, qslot, unitInfo, C, Q, db, D, dir, spOf, maxTax, kmerFormat,
+                                                         readCnt, total, buf, bufRank, region, err, winCap, win, lines,
+                                                         lineP, runOff, sortLo, stats, direct, dirOff, overflow, capShift,
+                                                         longList, longCap, longCnt, lineExt, upr, cnt64);
+        else
+            k_match<false, true><<<blocks, 256, 0, s>>>(qkey, qslot, unitInfo, C, Q, db, D, dir, spOf, maxTax, kmerFormat,
+                                                        readCnt, total, buf, bufRank, region, err, winCap, win, lines,
+                                                        lineP, runOff, sortLo, stats, direct, dirOff, overflow, capShift,
+                                                        longList, longCap, longCnt, nullptr, upr, cnt64);
     } else {
         const unsigned blocks = (unsigned)((Q + kMatchQ - 1) / kMatchQ);
-        k_match<true, kMatchQ / 256><<<blocks, 256, 0, s>>>(qkey, qslot, unitInfo, C, Q, db, D, dir, spOf,
+        k_match<true, false><<<blocks, 256, 0, s>>>(qkey, qslot, unitInfo, C, Q, db, D, dir, spOf,
                                                             maxTax, kmerFormat, readCnt, total, buf, bufRank, region,
                                                             err, winCap, win, lines, nullptr, nullptr, kQuerySortLo,
                                                             stats, direct, dirOff, overflow, capShift, nullptr, 0,
@@ -3889,9 +3317,6 @@ __device__ __forceinline__ bool sweep_query(uint64_t q, uint64_t key, uint32_t s
              (uint64_t)rk, (uint64_t)rk + c, 0, err);
     return true;
 }
-
-__device__ int g_abSweepCount = 0;  // MTB_AB_SWEEP_COUNT=1 (A/B only): k_sweep_ws without emission
-void set_ab_sweep_count(int on) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_abSweepCount), &on, sizeof(int)); }
 
 // tileQ[t] = the first sorted query of tile t's buckets (per batch: one coalesced pass, so a sweep
 // block reads its query range and its records' range in one round trip)
@@ -4149,19 +3574,6 @@ __global__ void __launch_bounds__(512) k_sweep_ws(const uint64_t* __restrict__ t
                 recs += n;
                 auto run = [&](const auto& vals, const auto& taxs) {
                     for (uint64_t q = d.q0 + lt; q < d.q1; q += 256) {
-                        if (g_abSweepCount) {  // A/B only: the sweep's LDS work alone (no emission: invalid results)
-                            const uint64_t key = qkey[q], aa = key & kAAMask, aa2 = aa + (1ull << 24);
-                            uint32_t p1 = 0, p2 = 0;
-                            for (uint32_t step = pow2; step > 0; step >>= 1) {
-                                const uint32_t i1 = p1 + step, i2 = p2 + step;
-                                if (i1 <= n && vals[i1 - 1] < aa) p1 = i1;
-                                if (i2 <= n && vals[i2 - 1] < aa2) p2 = i2;
-                            }
-                            uint64_t hi = p2;
-                            uint32_t thr = 0;
-                            hits += run_select(hamming_rows(key), vals, d.r0, (uint64_t)p1, hi, D, thr) != 0;
-                            continue;
-                        }
                         const uint32_t slot = qslot[q];
                         uint32_t p;
                         const ulonglong2 ur = reinterpret_cast<const ulonglong2*>(unitInfo)[slot_unit(slot, C, p)];

@@ -201,7 +201,7 @@ def test_end_to_end_batches(make_db, db_name):
 
 @pytest.mark.parametrize("db_name", ["fmt2", "fmt1"])
 @pytest.mark.parametrize("window", ["0", "0:gallop", "0:staged", "0:retry", "0:spill", "0:fine28", "0:unfused",
-                                    "0:nodigits", "0:atomiclines", "0:matchxcd", "0:nofast", "0:blockjoin", "0:pipejoin", "0:wave64join", "0:pairjoin", "0:wavepack", "0:nolink", "0:share", "0:bins", "0:binsover", "0:binsnodig", "0:ext", "0:atomicfirst", "0:ballot", "64",
+                                    "0:nodigits", "0:atomiclines", "0:nofast", "0:wavepack", "0:nolink", "0:bins", "0:binsover", "0:binsnodig", "0:ext", "0:atomicfirst", "0:ballot", "64",
                                     "6144", "6144:staged", "6144:spill", "6144:unfused", "0:nofilter", "6144:nofilter"])
 def test_match_window_paths(make_db, db_name, window, monkeypatch):
     """K4's search paths — DB window staged in LDS, or HBM search (the unstaged join: runs from the
@@ -215,7 +215,7 @@ def test_match_window_paths(make_db, db_name, window, monkeypatch):
     and the unstaged join over queries sorted on a 32-bit AA-rank prefix (MTB_SORT_LO_FINE=28, its
     own block line ranges and LDS staging). The unstaged default modes run k_join_uniform (the
     production join: uniform units, run index, direct output); "nofast" the same batch through
-    k_match's lean form; "blockjoin" / "pipejoin" through k_join_uniform's block-staged / resident-wave forms; "nolink" K1F through the probe lines alone (no link lines)."""
+    k_match's lean form; "nolink" K1F through the probe lines alone (no link lines)."""
     window, _, mode = window.partition(":")
     monkeypatch.setenv("MTB_SORT_LO_FINE", "28" if mode == "fine28" else "36")
     monkeypatch.setenv("MTB_MATCH_WINDOW", window)
@@ -226,13 +226,8 @@ def test_match_window_paths(make_db, db_name, window, monkeypatch):
     monkeypatch.setenv("MTB_RADIX_DIGITS", "0" if mode == "nodigits" else "1")  # K2 histograms from the keys
     # probe lines and run index built by per-k-mer global atomics (round 4's) instead of a wave per line
     monkeypatch.setenv("MTB_LINE_BUILD", "atomic" if mode == "atomiclines" else "wave")
-    monkeypatch.setenv("MTB_MATCH_XCD", "1" if mode == "matchxcd" else "0")  # K4 blocks per XCD eighth
-    monkeypatch.setenv("MTB_SHARE_RUNS", "1" if mode == "share" else "0")  # same-AA queries share one lookup
     # the production configuration through k_match's lean form instead of k_join_uniform (round 6)
     monkeypatch.setenv("MTB_JOIN_FAST", "0" if mode == "nofast" else "1")
-    # k_join_uniform's staging: per wave (the default), per block (round 6's first form), or resident waves
-    # with the next tile's lines and keys in flight (A/B)
-    monkeypatch.setenv("MTB_JOIN_WAVE", {"blockjoin": "0", "pipejoin": "2", "wave64join": "4", "pairjoin": "7"}.get(mode, "1"))
     # the fused K1F's one probe-line read per window instead of the link lines' one read per window pair
     monkeypatch.setenv("MTB_LINK_LINES", "0" if mode == "nolink" else "1")
     # the fused K1F packing its present windows per wave, no block barrier per group (A/B, round 6)

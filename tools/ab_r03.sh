@@ -3,9 +3,6 @@
 # kernel-trace --stats run plus separate FETCH_SIZE / WRITE_SIZE passes (tools/ab_summary.py):
 #   base      the default path
 #   k6group   K6 chooseBestTaxon on a 16-lane group per read (MTB_WAVE_TAXON=2) instead of a thread
-#   rankfree  K4 without the per-read rank atomic (MTB_AB_RANK_FREE=1: ranks are wrong and the results
-#             invalid; an upper bound of what removing the atomic can save in the join)
-#   dirfree   nor the read's stretch bounds (MTB_AB_RANK_FREE=2: no dirOff reads; invalid results)
 # Usage: tools/ab_r03.sh [variant ...]. Output: gpurun_out/r03/ab/<variant>/ab.json
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
@@ -15,9 +12,7 @@ CMD="bench.py --full --skip-config2 --steps 1 --warmup 1 --long-reads 0 --varian
 declare -A ENVS
 ENVS[base]="MTB_AB_NONE=1"
 ENVS[k6group]="MTB_WAVE_TAXON=2"
-ENVS[rankfree]="MTB_AB_RANK_FREE=1"
-ENVS[dirfree]="MTB_AB_RANK_FREE=2"
-for v in ${@:-base k6group rankfree}; do
+for v in ${@:-base k6group}; do
   D=$O/$v
   mkdir -p $D
   export ${ENVS[$v]}
