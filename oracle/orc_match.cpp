@@ -246,3 +246,19 @@ bool compareMatches(const mtb_match& a, const mtb_match& b) {
 void sortMatches(std::vector<mtb_match>& m) { __gnu_parallel::sort(m.begin(), m.end(), compareMatches); }
 
 }  // namespace orc
+
+// Pin hook (tests/test_ref_assign.py against tests/golden/ref_assign.npz, which the reference's own
+// KmerMatcher::compareDna produced): one query k-mer against n candidate k-mers. sel / sel_sum /
+// sel_ham (n entries each) get the selected candidates' indices, Hamming sums and per-codon Hammings.
+extern "C" int orc_pin_compare_dna(uint64_t query, const uint64_t* targets, uint64_t n, int frame, int kmer_format,
+                                   uint64_t* sel, uint8_t* sel_sum, uint16_t* sel_ham, uint64_t* n_sel) {
+    std::vector<uint64_t> t(targets, targets + n);
+    std::vector<uint8_t> hd, sum(n);
+    std::vector<size_t> idx(n);
+    std::vector<uint16_t> ham(n);
+    size_t k = 0;
+    orc::compareDna(query, t, hd, idx, sum, ham, k, (uint8_t)frame, kmer_format);
+    for (size_t i = 0; i < k; i++) { sel[i] = idx[i]; sel_sum[i] = sum[i]; sel_ham[i] = ham[i]; }
+    *n_sel = k;
+    return MTB_OK;
+}
