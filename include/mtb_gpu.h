@@ -287,6 +287,15 @@ int mtb_pin_eval(int device, int fn, const int64_t* param, const uint64_t* a, co
 int mtb_sort_pairs(int device, const uint64_t* keys, const uint32_t* vals, uint64_t n, int bit_lo, int bit_hi,
                    uint64_t* keys_out, uint32_t* vals_out);
 
+/* The same sort with 64-bit values, as the DB builder and K6's work lists run it (tests only:
+ * tests/test_radix.py). The passes are whole 8-bit digits from bit_lo up, so the sort key is bits
+ * [bit_lo, min(64, bit_lo + 8 * ceil((bit_hi - bit_lo) / 8))). filter != 0: pairs whose whole key is
+ * ~0 are dropped (first pass). gen_vals != 0: vals is not read, the values are the input positions
+ * (not with filter: MTB_ERR_ARG). keys_out / vals_out (n entries each) receive the *n_kept kept
+ * pairs, stable. */
+int mtb_sort_pairs64(int device, const uint64_t* keys, const uint64_t* vals, uint64_t n, int bit_lo, int bit_hi,
+                     int filter, int gen_vals, uint64_t* keys_out, uint64_t* vals_out, uint64_t* n_kept);
+
 /* Diagnostics (round 5): the opened DB's run-length lines (the unstaged join's runs without a
  * run-index read) checked against its run index for every present AA rank within their reach:
  * out[0] ranks checked, out[1] those the codes resolve, out[2] mismatches (MTB_ERR_INTERNAL when

@@ -2398,3 +2398,53 @@ extern "C" int mtb_sort_pairs(int device, const uint64_t* keys, const uint32_t* 
     HIP_TRY(hipMemcpy(vals_out, inB ? vb.p : va.p, 4 * n, hipMemcpyDeviceToHost));
     return MTB_OK;
 }
+
+// The same sort with 64-bit values (staged entry, tests only): radix_sort_pairs<uint64_t> as the DB
+// builder (mtb_build.hip: filter, then a plain 64-bit pass set) and K6's work lists (mtb_assign.hip:
+// gen_vals over bits [0, bits); filter over bits [32, 40)) call it, with the same scratch sizes and
+// the same knobs. The contract the tests hold it to:
+//  * the passes are whole 8-bit digits from bit_lo up, so the sort key is bits
+//    [bit_lo, min(64, bit_lo + 8 * ceil((bit_hi - bit_lo) / 8))) — a range whose width is no
+//    multiple of 8 is rounded up, and a digit that would reach past bit 63 is zero-extended;
+//  * every pass is stable: pairs of equal sort key keep their input order;
+//  * filter: a pair is dropped iff its whole key equals ~0 (kSentinel), whatever the bit range; the
+//    test is made in the first pass only (k_radix_hist<true> and k_radix_scatter<.., true, ..> agree
+//    on it), and *n_kept is what radix_sort_pairs returns. With every key a sentinel the first pass
+//    still runs and the (empty) result is on side B;
+//  * gen_vals: vals is not read (may be null); the values are the input positions 0 .. n - 1.
+//    No 64-bit call combines filter with gen_vals, so the entry refuses the pair.
+// keys_out / vals_out receive the *n_kept pairs of the side *inB names.
+extern "C" int mtb_sort_pairs64(int device, const uint64_t* keys, const uint64_t* vals, uint64_t n, int bit_lo,
+                                int bit_hi, int filter, int gen_vals, uint64_t* keys_out, uint64_t* vals_out,
+                                uint64_t* n_kept) {
+    if (!n_kept || (n && (!keys || (!vals && !gen_vals) || !keys_out || !vals_out))) { set_error("null argument"); return MTB_ERR_ARG; }
+    if (bit_lo < 0 || bit_hi > 64 || bit_lo >= bit_hi || n >= (1ull << 32)) { set_error("bad sort range"); return MTB_ERR_ARG; }
+    if (filter && gen_vals) { set_error("filter with gen_vals: no 64-bit sort runs so"); return MTB_ERR_ARG; }
+    *n_kept = 0;
+    if (!n) return MTB_OK;
+    HIP_TRY(hipSetDevice(device));
+    DevBuf ka, va, kb, vb, cnt, offs, tmp;
+    const uint64_t rc = radix_counts_elems(n + 1);
+    HIP_TRY(ka.ensure(8 * (n + 1)));
+    HIP_TRY(va.ensure(8 * (n + 1)));
+    HIP_TRY(kb.ensure(8 * (n + 1)));
+    HIP_TRY(vb.ensure(8 * (n + 1)));
+    HIP_TRY(cnt.ensure(4 * rc));
+    HIP_TRY(offs.ensure(8 * (rc + 1)));
+    HIP_TRY(tmp.ensure(8 * scan_tmp_elems(rc + n + 2)));
+    HIP_TRY(hipMemcpy(ka.p, keys, 8 * n, hipMemcpyHostToDevice));
+    if (!gen_vals) HIP_TRY(hipMemcpy(va.p, vals, 8 * n, hipMemcpyHostToDevice));
+    bool inB = false;
+    const uint64_t kept = radix_sort_pairs(ka.as<uint64_t>(), va.as<uint64_t>(), kb.as<uint64_t>(), vb.as<uint64_t>(), n,
+                                           bit_lo, bit_hi, filter != 0, gen_vals != 0, cnt.as<uint32_t>(),
+                                           offs.as<uint64_t>(), tmp.p, &inB, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    if (kept > n) { set_error("radix sort kept more pairs than it was given"); return MTB_ERR_HIP; }
+    if (kept) {
+        HIP_TRY(hipMemcpy(keys_out, inB ? kb.p : ka.p, 8 * kept, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(vals_out, inB ? vb.p : va.p, 8 * kept, hipMemcpyDeviceToHost));
+    }
+    *n_kept = kept;
+    return MTB_OK;
+}

@@ -19,27 +19,32 @@ def max_cov(n):
     return n - 2 if n % 3 == 2 else (n - 4 if n % 3 == 1 else n - 3)
 
 
-def frame_windows(seq: bytes, frame: int, fmt: int, syncmer: int, smer: int):
-    n = len(seq)
-    used = max_cov(n)
-    fwd = frame < 3
-    begin = frame if fwd else ((n % 3) - (frame % 3)) % 3
-    s, e = begin, begin + used - 1
-    aalen = used // 3
+def block_codons(seq: bytes, start: int, end: int, forward: bool, fmt: int):
+    """(aa, codon number) of the codons of seq[start..end] (end inclusive) in scan order: (end - start
+    + 1) // 3 codons (initScanner: aaLen = seqLen / 3), counted from the block's start when the strand
+    is forward in format 2 or reverse in format 1, from its end otherwise; the bases left over lie at
+    the far side. A reverse-strand codon is the reverse complement of its three bases."""
+    aalen = (end - start + 1) // 3
+    from_left = forward == (fmt == 2)
     cods = []
     for j in range(aalen):
-        if fmt == 2:
-            if fwd:
-                t = [ATCG[seq[s + 3 * j + k]] for k in range(3)]
-            else:
-                t = [IRCT[ATCG[seq[e - 3 * j - k]]] for k in range(3)]
+        lo = start + 3 * j if from_left else end - 3 * j - 2
+        if forward:
+            t = [ATCG[seq[lo + k]] for k in range(3)]
         else:
-            if fwd:
-                t = [ATCG[seq[e - 3 * j - 2 + k]] for k in range(3)]
-            else:
-                t = [IRCT[ATCG[seq[s + 3 * j + 2 - k]]] for k in range(3)]
+            t = [IRCT[ATCG[seq[lo + 2 - k]]] for k in range(3)]
         key = tuple(code(x) for x in t)
         cods.append((AA[key], NUM[key]))
+    return cods
+
+
+def block_windows(seq: bytes, start: int, end: int, forward: bool, fmt: int, syncmer: int, smer: int):
+    """(value, pos) of every window the scanner of (fmt, syncmer) emits over the block seq[start..end]
+    on the given strand, in scan order (MetamerScanner / OldMetamerScanner::next, KmerScanner.h:82-181;
+    SyncmerScanner.h:36-102)."""
+    s, e = start, end
+    cods = block_codons(seq, start, end, forward, fmt)
+    aalen = len(cods)
     out = []
     for p in range(aalen - 7):
         w = cods[p:p + 8]
@@ -66,9 +71,17 @@ def frame_windows(seq: bytes, frame: int, fmt: int, syncmer: int, smer: int):
             aa = 0
             for a, _ in w:
                 aa = aa * 21 + a
-        pos = s + 3 * p if (fwd == (fmt == 2)) else e - 3 * (p + 8) + 1
-        out.append(((aa << 24) | dna, pos, frame))
+        pos = s + 3 * p if (forward == (fmt == 2)) else e - 3 * (p + 8) + 1
+        out.append(((aa << 24) | dna, pos))
     return out
+
+
+def frame_windows(seq: bytes, frame: int, fmt: int, syncmer: int, smer: int):
+    n = len(seq)
+    used = max_cov(n)
+    fwd = frame < 3
+    begin = frame if fwd else ((n % 3) - (frame % 3)) % 3
+    return [(v, pos, frame) for v, pos in block_windows(seq, begin, begin + used - 1, fwd, fmt, syncmer, smer)]
 
 
 def read_kmers(seq1: bytes, seq2, fmt, syncmer=0, smer=5):

@@ -16,6 +16,7 @@ from metabuli_work_amd._abi import default_params
 from metabuli_work_amd._lib import MtbError, lib
 from metabuli_work_amd.dbbuild import HostDb, build_db, merge_db_dirs, merge_dbs, merge_last_ms, subset_genomes, update_db
 from tests import oracle_ctypes as oc
+from tests.dbref import Tree, decode_diff, diff_words
 
 pytestmark = pytest.mark.gpu
 
@@ -25,30 +26,6 @@ _TMP = tempfile.TemporaryDirectory(prefix="mtb_merge_")
 
 
 # ---- numpy restatements (expected values never come from the code under test) -------------------
-def decode_diff(diff):
-    """getNextTargetKmer over a whole diffIdx: the k-mer values."""
-    w = np.asarray(diff, np.uint64)
-    if len(w) == 0:
-        return np.zeros(0, np.uint64)
-    term = (w >> np.uint64(15)).astype(bool)
-    ends = np.flatnonzero(term)
-    gid = np.concatenate([[0], np.cumsum(term)[:-1]]).astype(np.int64)
-    sh = (15 * (ends[gid] - np.arange(len(w)))).astype(np.uint64)
-    delta = np.zeros(len(ends), np.uint64)
-    np.add.at(delta, gid, (w & np.uint64(0x7FFF)) << sh)
-    return np.cumsum(delta, dtype=np.uint64)
-
-
-def diff_words(values):
-    """Words getDiffIdx writes per k-mer."""
-    v = np.asarray(values, np.uint64)
-    d = np.diff(np.concatenate([[np.uint64(0)], v]).astype(np.uint64))
-    n = np.ones(len(v), np.int64)
-    for k in range(1, 5):
-        n += (d >> np.uint64(15 * k)) > 0
-    return n
-
-
 def merge_rule_split(values, n_before, split_num):
     """IndexCreator.h:432-447 restated: the split entries a merge writes, sizeOfSplit =
     numOfKmerBeforeMerge / (splitNum - 1)."""
@@ -71,36 +48,6 @@ def merge_rule_split(values, n_before, split_num):
             check = 1
             offset_idx += 1
     return split
-
-
-class Tree:
-    """Species and LCA of the synthetic taxonomy, by parent walks."""
-
-    def __init__(self, taxo):
-        self.parent = dict(zip(taxo.taxid.tolist(), taxo.parent.tolist()))
-        self.rank = dict(zip(taxo.taxid.tolist(), taxo.rank))
-        self.depth = {}
-        for t in self.parent:
-            d, x = 0, t
-            while x != 1:
-                x = self.parent[x]
-                d += 1
-            self.depth[t] = d
-        self.sp = np.zeros(int(taxo.taxid.max()) + 1, np.int64)
-        for t in self.parent:
-            x = t
-            while x != 1 and self.rank[x] != "species":
-                x = self.parent[x]
-            self.sp[t] = x if self.rank[x] == "species" else 0
-
-    def lca(self, a, b):
-        while a != b:
-            da, db = self.depth[a], self.depth[b]
-            if da >= db:
-                a = self.parent[a]
-            if db >= da:
-                b = self.parent[b]
-        return a
 
 
 def expected_merge(tree, parts):
