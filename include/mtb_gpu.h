@@ -296,6 +296,12 @@ int mtb_sort_pairs(int device, const uint64_t* keys, const uint32_t* vals, uint6
 int mtb_sort_pairs64(int device, const uint64_t* keys, const uint64_t* vals, uint64_t n, int bit_lo, int bit_hi,
                      int filter, int gen_vals, uint64_t* keys_out, uint64_t* vals_out, uint64_t* n_kept);
 
+/* The device-wide exclusive scan alone (tests only: tests/test_scan_edges.py): out[i] = in[0] + ..
+ * + in[i - 1] for i = 0 .. n (n + 1 entries; out[n] is the total). out_bits 64: out is uint64_t, the
+ * form of every per-read offset array. out_bits 32: out is uint32_t, the radix sort's form; the
+ * caller keeps the total below 2^32 (sums past it come out modulo 2^32). Host arrays. */
+int mtb_scan_u32(int device, const uint32_t* in, uint64_t n, int out_bits, void* out);
+
 /* Diagnostics (round 5): the opened DB's run-length lines (the unstaged join's runs without a
  * run-index read) checked against its run index for every present AA rank within their reach:
  * out[0] ranks checked, out[1] those the codes resolve, out[2] mismatches (MTB_ERR_INTERNAL when

@@ -25,7 +25,7 @@ EXPORTED = [
     "mtb_ctx_device", "mtb_start_classify_multi", "mtb_mask_reads", "mtb_workspace_bytes", "mtb_set_workspace_cap",
     "mtb_open_phases", "mtb_start_classify_partitioned", "mtb_release_workspace", "mtb_hamming", "mtb_memcpy",
     "mtb_line_ext_check", "mtb_link_check", "mtb_pin_eval", "mtb_sort_pairs", "mtb_sort_pairs64",
-    "mtb_merge_db", "mtb_merge_db_dirs", "mtb_merge_last_ms", "mtb_merge_tile_items",
+    "mtb_merge_db", "mtb_merge_db_dirs", "mtb_merge_last_ms", "mtb_merge_tile_items", "mtb_scan_u32",
 ]
 
 
@@ -95,6 +95,7 @@ def lib() -> ctypes.CDLL:
     L.mtb_pin_eval.argtypes = [i32, i32, vp, vp, vp, u64, vp, vp]
     L.mtb_sort_pairs.argtypes = [i32, vp, vp, u64, i32, i32, vp, vp]
     L.mtb_sort_pairs64.argtypes = [i32, vp, vp, u64, i32, i32, i32, i32, vp, vp, vp]
+    L.mtb_scan_u32.argtypes = [i32, vp, u64, i32, vp]
     L.mtb_memcpy.argtypes = [vp, vp, u64]
     L.mtb_line_ext_check.argtypes = [vp, vp]
     L.mtb_link_check.argtypes = [vp, vp]

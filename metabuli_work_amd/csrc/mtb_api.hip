@@ -2448,3 +2448,26 @@ extern "C" int mtb_sort_pairs64(int device, const uint64_t* keys, const uint64_t
     *n_kept = kept;
     return MTB_OK;
 }
+
+// The device-wide exclusive scan alone (staged entry, tests only): out[i] = in[0] + .. + in[i - 1] for
+// i = 0 .. n, so out has n + 1 entries and out[n] is the total. out_bits 64: exclusive_scan_u32, the
+// form every per-read offset array takes (uint64_t out). out_bits 32: exclusive_scan_u32_out32, the
+// radix sort's form (uint32_t out); the caller keeps the total below 2^32, as the sort does (sums past
+// it come out modulo 2^32). Host arrays; n = 0 writes the single entry 0.
+extern "C" int mtb_scan_u32(int device, const uint32_t* in, uint64_t n, int out_bits, void* out) {
+    if (!out || (n && !in)) { set_error("null argument"); return MTB_ERR_ARG; }
+    if (out_bits != 32 && out_bits != 64) { set_error("out_bits is 32 or 64"); return MTB_ERR_ARG; }
+    HIP_TRY(hipSetDevice(device));
+    const uint64_t ob = (uint64_t)out_bits / 8;
+    DevBuf di, dout, tmp;
+    HIP_TRY(di.ensure(4 * std::max<uint64_t>(n, 1)));
+    HIP_TRY(dout.ensure(ob * (n + 1)));
+    HIP_TRY(tmp.ensure(8 * scan_tmp_elems(n)));
+    if (n) HIP_TRY(hipMemcpy(di.p, in, 4 * n, hipMemcpyHostToDevice));
+    if (out_bits == 32) exclusive_scan_u32_out32(di.as<uint32_t>(), n, dout.as<uint32_t>(), tmp.p, nullptr);
+    else exclusive_scan_u32(di.as<uint32_t>(), n, dout.as<uint64_t>(), tmp.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout.p, ob * (n + 1), hipMemcpyDeviceToHost));
+    return MTB_OK;
+}

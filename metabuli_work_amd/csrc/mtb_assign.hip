@@ -347,6 +347,8 @@ __device__ __forceinline__ void lds_sort_keys_n(K* a, int n, int lane) {
 // (species, frame, pos) — one query k-mer matching several DB k-mers of the species — take their
 // places inside the tie by (hamming, dna, target), the rest of compareMatches' order, counted from
 // the LDS records (ties are short runs of neighbours). Same output as prune_then_sort.
+// A segment whose species are all below 2^24 and positions below 2^28 (every real short-read batch)
+// needs no ranks: species:24 | frame:3 | pos:28 | record:9 is 64 bits, in the same order.
 template <int E>
 struct RankLds {
     union {
@@ -407,36 +409,50 @@ __device__ __forceinline__ void prune_rank_sort(const In& in, mtb_match* __restr
     bool live[E];
 #pragma unroll
     for (int sl = 0; sl < E; sl++) live[sl] = 64 * sl + lane < n && (spKey[ss[sl]] & kLive);
-    // the live species, sorted: their ranks (pairKey and pairCnt are dead now)
+    // direct (wave-uniform): every species of the segment is below 2^24 and every position below 2^28,
+    // so species:24 | frame:3 | pos:28 | record:9 is a 64-bit key by itself. The rank is monotone in
+    // the species, so the order, the ties (>> 9) and the output are the rank key's, without the species
+    // list, its sort and the rank pass.
+    uint32_t wide = 0;
+#pragma unroll
+    for (int sl = 0; sl < E; sl++) wide |= (uint32_t)(h[sl] >> 56) | ((uint32_t)(h[sl] >> 28) & 1u);
+    const bool direct = __ballot(wide != 0) == 0;
     const uint64_t lt = (1ull << lane) - 1;
-    uint32_t* spList = pairCnt;
-    int S = 0;
-    for (uint32_t i0 = 0; i0 < T; i0 += 64) {
-        const uint32_t v = spKey[i0 + lane];
-        const bool lv = (v & kLive) != 0;
-        const uint64_t m = __ballot(lv);
-        if (lv) spList[S + (int)__popcll(m & lt)] = v & ~kLive;
-        S += (int)__popcll(m);
+    if (!direct) {
+        // the live species, sorted: their ranks (pairKey and pairCnt are dead now)
+        uint32_t* spList = pairCnt;
+        int S = 0;
+        for (uint32_t i0 = 0; i0 < T; i0 += 64) {
+            const uint32_t v = spKey[i0 + lane];
+            const bool lv = (v & kLive) != 0;
+            const uint64_t m = __ballot(lv);
+            if (lv) spList[S + (int)__popcll(m & lt)] = v & ~kLive;
+            S += (int)__popcll(m);
+        }
+        __syncthreads();
+        lds_sort_keys_n<E, uint32_t>(spList, S, lane);
+        __syncthreads();
+        for (int e = lane; e < S; e += 64) {  // rank of each live species, stored at its table slot
+            const uint32_t v = spList[e];
+            uint32_t i = (uint32_t)(((uint64_t)v * 0x9E3779B97F4A7C15ull) >> 40) & (T - 1);
+            while ((spKey[i] & ~kLive) != v) i = (i + 1) & (T - 1);
+            pairKey[i] = (uint32_t)e;
+        }
+        __syncthreads();
     }
-    __syncthreads();
-    lds_sort_keys_n<E, uint32_t>(spList, S, lane);
-    __syncthreads();
-    for (int e = lane; e < S; e += 64) {  // rank of each live species, stored at its table slot
-        const uint32_t v = spList[e];
-        uint32_t i = (uint32_t)(((uint64_t)v * 0x9E3779B97F4A7C15ull) >> 40) & (T - 1);
-        while ((spKey[i] & ~kLive) != v) i = (i + 1) & (T - 1);
-        pairKey[i] = (uint32_t)e;
-    }
-    __syncthreads();
+    const int frameAt = direct ? 37 : 38;  // the key's frame field; pos is bits [9, frameAt)
     uint64_t key[E];
     int nLive = 0;
 #pragma unroll
     for (int sl = 0; sl < E; sl++) {
         const uint64_t m = __ballot(live[sl]);
         const uint32_t p = (uint32_t)(nLive + (int)__popcll(m & lt));
-        key[sl] = live[sl] ? ((uint64_t)pairKey[ss[sl]] << 41 | ((h[sl] >> 29) & 7ull) << 38 |
-                              (h[sl] & 0x1FFFFFFFull) << 9 | p)
-                           : 0;
+        if (direct)  // h = species:32 | frame:3 | pos:29 with bit 28 and the top byte clear
+            key[sl] = live[sl] ? ((h[sl] >> 29) << 37 | (h[sl] & 0x0FFFFFFFull) << 9 | p) : 0;
+        else
+            key[sl] = live[sl] ? ((uint64_t)pairKey[ss[sl]] << 41 | ((h[sl] >> 29) & 7ull) << 38 |
+                                  (h[sl] & 0x1FFFFFFFull) << 9 | p)
+                               : 0;
         nLive += (int)__popcll(m);
     }
     __syncthreads();  // the tables are dead: their bytes take the live records and keys
@@ -462,7 +478,7 @@ __device__ __forceinline__ void prune_rank_sort(const In& in, mtb_match* __restr
         for (int j = e - 1; j >= 0 && (L.c.key[j] >> 9) == pre; j--) at -= L.c.lo[L.c.key[j] & 511u] > lo;
         for (int j = e + 1; j < nLive && (L.c.key[j] >> 9) == pre; j++) at += L.c.lo[L.c.key[j] & 511u] < lo;
         mtb_match m;
-        m.qinfo = ((k >> 38) & 7ull) << 61 | seqBits | (uint32_t)((k >> 9) & 0x1FFFFFFFu);
+        m.qinfo = ((k >> frameAt) & 7ull) << 61 | seqBits | (uint32_t)((k >> 9) & ((1ull << (frameAt - 9)) - 1));
         m.target_id = (uint32_t)lo;
         m.species_id = L.c.sp[p];
         m.dna_encoding = (uint32_t)(lo >> 32) & 0xFFFFFFu;
@@ -2953,8 +2969,9 @@ __global__ void __launch_bounds__(64) k_choose_taxon_wave(const mtb_match* __res
 // The same for short reads with kGroupLanes lanes per read (16 reads per 256-thread block): the
 // species-run scan, the tie set and filterRedundantMatches' per-quotient reduction as in the wave
 // kernel, on a 16-lane group with per-group LDS tables (kGroupQ quotients, kGroupHash taxa); the
-// group's first lane runs the tail. A read whose quotients or taxa do not fit takes the serial
-// filter on that lane. Block-wide barriers order the LDS phases (every thread reaches them).
+// group's first lane runs the tail on a taxCnt list the group wrote in taxon order. A read whose
+// quotients or taxa do not fit takes the serial filter on that lane. The LDS phases are ordered within
+// the wave (group_lds_order): the block's 16 reads do not wait for each other.
 constexpr int kGroupLanes = 16;
 constexpr int kGroupQ = 128;    // quotients of a read (a 2 x 150 bp pair at dnaShift 3: 101)
 constexpr int kGroupHash = 64;  // distinct taxa of one read's taxCnt
@@ -2968,6 +2985,16 @@ __device__ __forceinline__ long group_sum_l(long x) {
 #pragma unroll
     for (int d = kGroupLanes / 2; d > 0; d >>= 1) x += __shfl_xor(x, d, kGroupLanes);
     return x;
+}
+
+// Orders the LDS phases of k_choose_taxon_group: a group's tables are private to its 16 lanes, all in
+// one wave, and a wave's LDS operations complete in program order, so no block barrier is needed —
+// only that the compiler keeps the phases' LDS accesses on their sides of this point. Every lane of
+// the wave reaches it (invalid reads included).
+__device__ __forceinline__ void group_lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 __global__ void __launch_bounds__(256) k_choose_taxon_group(const mtb_match* __restrict__ M,
@@ -3066,7 +3093,7 @@ __global__ void __launch_bounds__(256) k_choose_taxon_group(const mtb_match* __r
         }
         if (gl == 0) gFlag[g] = 0;
     }
-    __syncthreads();
+    group_lds_order();
     if (lds) {
         for (long i = gl; i < nb; i += kGroupLanes) {
             const uint32_t q = info_pos(B[i].qinfo) / dnaShift;
@@ -3077,7 +3104,7 @@ __global__ void __launch_bounds__(256) k_choose_taxon_group(const mtb_match* __r
             atomicMin(&qw[g][q], (uint32_t)B[i].hamming << 24 | 0xFFFFFFu);
         }
     }
-    __syncthreads();
+    group_lds_order();
     const bool ok = lds && !gFlag[g];
     if (ok) {
         for (long i = gl; i < nb; i += kGroupLanes) {
@@ -3096,7 +3123,7 @@ __global__ void __launch_bounds__(256) k_choose_taxon_group(const mtb_match* __r
             }
         }
     }
-    __syncthreads();
+    group_lds_order();
     if (ok) {
         for (long q = gl; q <= maxQ; q += kGroupLanes) {
             const uint32_t wq = qw[g][q];
@@ -3118,10 +3145,12 @@ __global__ void __launch_bounds__(256) k_choose_taxon_group(const mtb_match* __r
             }
         }
     }
-    __syncthreads();
+    group_lds_order();
     mtb_taxcnt* tc = tcP + base;  // capacity n
     long nTc = -1;                // -1: the serial filter
-    if (ok && !gFlag[g]) {        // entries out in slot order (std::map order on the first lane below)
+    const bool packed = ok && !gFlag[g];
+    if (packed) {  // the entries packed in slot order into qw[g] (dead now) as (taxon, count) pairs
+        static_assert(2 * kGroupHash <= kGroupQ, "the packed taxa fit the quotient table");
         long at = 0;
         for (int k0 = 0; k0 < kGroupHash; k0 += kGroupLanes) {
             const int k = k0 + gl;
@@ -3129,12 +3158,22 @@ __global__ void __launch_bounds__(256) k_choose_taxon_group(const mtb_match* __r
             const uint32_t m = (uint32_t)(__ballot(v) >> gLane0) & 0xFFFFu;
             if (v) {
                 const long p = at + (long)__popc(m & ((1u << gl) - 1));
-                tc[p].tax_id = hk[g][k];
-                tc[p].count = hc[g][k];
+                qw[g][2 * p] = (uint32_t)hk[g][k];
+                qw[g][2 * p + 1] = hc[g][k];
             }
             at += (long)__popc(m);
         }
         nTc = at;
+    }
+    group_lds_order();
+    if (packed) {  // std::map order: an entry's place is the number of smaller taxa (they are distinct)
+        for (long e = gl; e < nTc; e += kGroupLanes) {
+            const int32_t t = (int32_t)qw[g][2 * e];
+            long at = 0;
+            for (long j = 0; j < nTc; j++) at += (int32_t)qw[g][2 * j] < t;
+            tc[at].tax_id = t;
+            tc[at].count = qw[g][2 * e + 1];
+        }
     }
     if (gl != 0 || !valid) return;
     if (!filter) {
@@ -3146,19 +3185,7 @@ __global__ void __launch_bounds__(256) k_choose_taxon_group(const mtb_match* __r
         results[r] = res;
         return;
     }
-    if (nTc < 0) {
-        nTc = filter_redundant_serial(M, bestFirst, bestSecond, runGroup[bestRun], gStart, dnaShift, tax, tc);
-    } else {
-        for (long a = 1; a < nTc; a++) {
-            mtb_taxcnt v = tc[a];
-            long b = a;
-            while (b > 0 && tc[b - 1].tax_id > v.tax_id) {
-                tc[b] = tc[b - 1];
-                b--;
-            }
-            tc[b] = v;
-        }
-    }
+    if (nTc < 0) nTc = filter_redundant_serial(M, bestFirst, bestSecond, runGroup[bestRun], gStart, dnaShift, tax, tc);
     classify_tail(res, tc, nTc, spTotal, bestTax, readLength, cfg, tax, cladeP + base * cladePerMatch,
                   n * (long)cladePerMatch);
     results[r] = res;

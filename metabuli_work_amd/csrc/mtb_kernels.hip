@@ -48,14 +48,45 @@ __device__ __forceinline__ unsigned long long block_exclusive_scan(unsigned long
 constexpr int kScanItems = 16;
 constexpr int kScanTile = kBlock * kScanItems;
 
+// A full tile whose arrays are 16-B aligned (vec; scan_impl decides) is read and written as 16-B
+// vectors: the tile is kScanQuads stretches of kBlock quads, thread t holding quad t of each, so a
+// wave's load or store is one contiguous stretch. The last tile, and unaligned arrays, keep the
+// guarded element-wise path. Sums are exact integers, so both give the same values.
+constexpr int kScanQuads = kScanItems / 4;
+
+__device__ __forceinline__ void scan_load_quad(const uint32_t* p, unsigned long long (&v)[4]) {
+    const uint4 x = *reinterpret_cast<const uint4*>(p);
+    v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
+}
+__device__ __forceinline__ void scan_load_quad(const uint64_t* p, unsigned long long (&v)[4]) {
+    const ulonglong2 a = reinterpret_cast<const ulonglong2*>(p)[0], b = reinterpret_cast<const ulonglong2*>(p)[1];
+    v[0] = a.x, v[1] = a.y, v[2] = b.x, v[3] = b.y;
+}
+__device__ __forceinline__ void scan_store_quad(uint32_t* p, const unsigned long long (&v)[4]) {
+    *reinterpret_cast<uint4*>(p) = make_uint4((uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2], (uint32_t)v[3]);
+}
+__device__ __forceinline__ void scan_store_quad(uint64_t* p, const unsigned long long (&v)[4]) {
+    reinterpret_cast<ulonglong2*>(p)[0] = make_ulonglong2(v[0], v[1]);
+    reinterpret_cast<ulonglong2*>(p)[1] = make_ulonglong2(v[2], v[3]);
+}
+
 template <typename T>
-__global__ void k_scan_tiles(const T* __restrict__ in, uint64_t n, unsigned long long* __restrict__ tileSum) {
+__global__ void __launch_bounds__(kBlock) k_scan_tiles(const T* __restrict__ in, uint64_t n, int vec,
+                                                       unsigned long long* __restrict__ tileSum) {
     const uint64_t base = (uint64_t)blockIdx.x * kScanTile;
     unsigned long long s = 0;
+    if (vec && base + kScanTile <= n) {
+        unsigned long long v[kScanQuads][4];
 #pragma unroll
-    for (int k = 0; k < kScanItems; k++) {
-        uint64_t i = base + (uint64_t)k * kBlock + threadIdx.x;
-        if (i < n) s += (unsigned long long)in[i];
+        for (int q = 0; q < kScanQuads; q++) scan_load_quad(in + base + ((uint64_t)q * kBlock + threadIdx.x) * 4, v[q]);
+#pragma unroll
+        for (int q = 0; q < kScanQuads; q++) s += v[q][0] + v[q][1] + v[q][2] + v[q][3];
+    } else {
+#pragma unroll
+        for (int k = 0; k < kScanItems; k++) {
+            uint64_t i = base + (uint64_t)k * kBlock + threadIdx.x;
+            if (i < n) s += (unsigned long long)in[i];
+        }
     }
     unsigned long long tot;
     block_exclusive_scan(s, &tot);
@@ -76,40 +107,78 @@ __global__ void k_scan_tile_sums(unsigned long long* __restrict__ tileSum, uint6
     if (threadIdx.x == 0) tileSum[nTiles] = carry;
 }
 
-template <typename T>
-__global__ void k_scan_apply(const T* __restrict__ in, uint64_t n, const unsigned long long* __restrict__ tileSum,
-                             uint64_t* __restrict__ out) {
-    // Thread-contiguous items so each tile is scanned in element order.
-    const uint64_t base = (uint64_t)blockIdx.x * kScanTile + (uint64_t)threadIdx.x * kScanItems;
-    unsigned long long v[kScanItems];
-    unsigned long long s = 0;
+// O: the output's type. uint32_t only where the caller knows the total fits 32 bits (the sums are
+// formed in 64 bits and truncated on the way out).
+template <typename T, typename O>
+__global__ void __launch_bounds__(kBlock) k_scan_apply(const T* __restrict__ in, uint64_t n, int vec,
+                                                       const unsigned long long* __restrict__ tileSum,
+                                                       O* __restrict__ out) {
+    const uint64_t tile0 = (uint64_t)blockIdx.x * kScanTile;
+    if (vec && tile0 + kScanTile <= n) {
+        // stretch q of the tile = its quads [q * kBlock, (q + 1) * kBlock), scanned in (stretch, wave, lane) order
+        __shared__ unsigned long long qSum[kScanQuads][kWaves];
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        unsigned long long v[kScanQuads][4], inc[kScanQuads];
 #pragma unroll
-    for (int k = 0; k < kScanItems; k++) {
-        uint64_t i = base + k;
-        v[k] = i < n ? (unsigned long long)in[i] : 0ull;
-        s += v[k];
-    }
-    unsigned long long tot;
-    unsigned long long run = block_exclusive_scan(s, &tot) + tileSum[blockIdx.x];
+        for (int q = 0; q < kScanQuads; q++) scan_load_quad(in + tile0 + ((uint64_t)q * kBlock + threadIdx.x) * 4, v[q]);
 #pragma unroll
-    for (int k = 0; k < kScanItems; k++) {
-        uint64_t i = base + k;
-        if (i < n) out[i] = run;
-        run += v[k];
+        for (int q = 0; q < kScanQuads; q++) {
+            inc[q] = wave_inclusive_scan(v[q][0] + v[q][1] + v[q][2] + v[q][3]);
+            if (lane == 63) qSum[q][w] = inc[q];
+        }
+        __syncthreads();
+        unsigned long long carry = tileSum[blockIdx.x];
+#pragma unroll
+        for (int q = 0; q < kScanQuads; q++) {
+            unsigned long long before = 0, all = 0;
+#pragma unroll
+            for (int i = 0; i < kWaves; i++) {
+                const unsigned long long x = qSum[q][i];
+                if (i < w) before += x;
+                all += x;
+            }
+            unsigned long long o[4];
+            o[0] = carry + before + inc[q] - (v[q][0] + v[q][1] + v[q][2] + v[q][3]);
+            o[1] = o[0] + v[q][0];
+            o[2] = o[1] + v[q][1];
+            o[3] = o[2] + v[q][2];
+            scan_store_quad(out + tile0 + ((uint64_t)q * kBlock + threadIdx.x) * 4, o);
+            carry += all;
+        }
+    } else {
+        // Thread-contiguous items so the tile is scanned in element order.
+        const uint64_t base = tile0 + (uint64_t)threadIdx.x * kScanItems;
+        unsigned long long v[kScanItems];
+        unsigned long long s = 0;
+#pragma unroll
+        for (int k = 0; k < kScanItems; k++) {
+            uint64_t i = base + k;
+            v[k] = i < n ? (unsigned long long)in[i] : 0ull;
+            s += v[k];
+        }
+        unsigned long long tot;
+        unsigned long long run = block_exclusive_scan(s, &tot) + tileSum[blockIdx.x];
+#pragma unroll
+        for (int k = 0; k < kScanItems; k++) {
+            uint64_t i = base + k;
+            if (i < n) out[i] = (O)run;
+            run += v[k];
+        }
     }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == kBlock - 1) out[n] = tileSum[gridDim.x];
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == kBlock - 1) out[n] = (O)tileSum[gridDim.x];
 }
 
-template <typename T>
-static void scan_impl(const T* in, uint64_t n, uint64_t* out, unsigned long long* tmp, hipStream_t s) {
+template <typename T, typename O>
+static void scan_impl(const T* in, uint64_t n, O* out, unsigned long long* tmp, hipStream_t s) {
     uint64_t tiles = (n + kScanTile - 1) / kScanTile;
     if (tiles == 0) {
-        hipMemsetAsync(out, 0, sizeof(uint64_t), s);
+        hipMemsetAsync(out, 0, sizeof(O), s);
         return;
     }
-    k_scan_tiles<T><<<(unsigned)tiles, kBlock, 0, s>>>(in, n, tmp);
+    const int vec = (((uintptr_t)in | (uintptr_t)out) & 15u) == 0;
+    k_scan_tiles<T><<<(unsigned)tiles, kBlock, 0, s>>>(in, n, vec, tmp);
     k_scan_tile_sums<<<1, kBlock, 0, s>>>(tmp, tiles);
-    k_scan_apply<T><<<(unsigned)tiles, kBlock, 0, s>>>(in, n, tmp, out);
+    k_scan_apply<T, O><<<(unsigned)tiles, kBlock, 0, s>>>(in, n, vec, tmp, out);
 }
 
 uint64_t scan_tmp_elems(uint64_t n) { return (n + kScanTile - 1) / kScanTile + 1; }
@@ -164,10 +233,13 @@ void launch_run_starts(const uint8_t* flags, const uint64_t* mOff, const uint64_
     if (nReads) k_run_starts<<<(nReads + 3) / 4, 256, 0, s>>>(flags, mOff, grpOff, runOff, nReads, gStart, sStart, runGroup);
 }
 void exclusive_scan_u32(const uint32_t* in, uint64_t n, uint64_t* out, void* tmp, hipStream_t s) {
-    scan_impl<uint32_t>(in, n, out, (unsigned long long*)tmp, s);
+    scan_impl<uint32_t, uint64_t>(in, n, out, (unsigned long long*)tmp, s);
+}
+void exclusive_scan_u32_out32(const uint32_t* in, uint64_t n, uint32_t* out, void* tmp, hipStream_t s) {
+    scan_impl<uint32_t, uint32_t>(in, n, out, (unsigned long long*)tmp, s);
 }
 void exclusive_scan_u64(const uint64_t* in, uint64_t n, uint64_t* out, void* tmp, hipStream_t s) {
-    scan_impl<uint64_t>(in, n, out, (unsigned long long*)tmp, s);
+    scan_impl<uint64_t, uint64_t>(in, n, out, (unsigned long long*)tmp, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -629,7 +701,7 @@ __global__ void __launch_bounds__(256) k_radix_scatter(const uint64_t* __restric
                                                        uint32_t nTiles, uint64_t* __restrict__ keysOut,
                                                        V* __restrict__ valsOut, uint8_t* __restrict__ digOut,
                                                        int nextShift, int xcdMap, const uint64_t* __restrict__ tab,
-                                                       int atomicRank) {
+                                                       int atomicRank, int offs32) {
     constexpr int kItems = TILE / kBlock, kSlice = 64 * kItems;
     __shared__ uint64_t sKV[TILE];  // keys, then (after they are written out) values
     __shared__ uint8_t sDig[TILE];
@@ -653,7 +725,9 @@ __global__ void __launch_bounds__(256) k_radix_scatter(const uint64_t* __restric
     const uint64_t base = tBase + (uint64_t)w * kSlice;
     // the digit bases: one strided load per lane, issued first so its latency hides behind the
     // key loads (a dependent load per key in the write-out loop was the old bottleneck)
-    const uint64_t digitBase = offs[(uint64_t)tid * nTiles + tile];
+    // offs32: the scan wrote 4-B offsets (a sort of fewer than 2^32 pairs): half the bytes of this gather
+    const uint64_t digitBase = offs32 ? reinterpret_cast<const uint32_t*>(offs)[(uint64_t)tid * nTiles + tile]
+                                      : offs[(uint64_t)tid * nTiles + tile];
     for (int x = tid; x < kWaves * 256; x += kBlock) (&waveHist[0][0])[x] = 0;
     if (atomicRank & 4)
         for (int x = tid; x < kWaves * 256; x += kBlock) sKV[x] = 0;  // the digits' lane masks (below)
@@ -857,7 +931,10 @@ uint64_t radix_sort_pairs(uint64_t* keysA, V* valsA, uint64_t* keysB, V* valsB, 
         } else if (digits) k_radix_hist_dig<<<nTiles, kBlock, 0, s>>>(di, cur, counts, nTiles, nullptr);
         else if (f) k_radix_hist<true><<<nTiles, kBlock, 0, s>>>(ki, cur, shift, counts, nTiles);
         else k_radix_hist<false><<<nTiles, kBlock, 0, s>>>(ki, cur, shift, counts, nTiles);
-        exclusive_scan_u32(counts, 256ull * nTiles, offs, scanTmp, s);
+        // every offset is at most cur: below 2^32 pairs the scan writes 4-B offsets into the same buffer
+        const int o32 = cur < (1ull << 32);
+        if (o32) exclusive_scan_u32_out32(counts, 256ull * nTiles, reinterpret_cast<uint32_t*>(offs), scanTmp, s);
+        else exclusive_scan_u32(counts, 256ull * nTiles, offs, scanTmp, s);
         uint8_t* dOut = digits && shift + 8 < bitHi ? dg : nullptr;
         // MTB_RADIX_XCD=0 (A/B, read per sort): tiles in block order instead of one contiguous eighth per XCD
         const char* xe = getenv("MTB_RADIX_XCD");
@@ -867,18 +944,19 @@ uint64_t radix_sort_pairs(uint64_t* keysA, V* valsA, uint64_t* keysB, V* valsB, 
         const char* fe = getenv("MTB_RADIX_FULLTILE");
         const int ar = (first && unstableFirst ? 1 : 0) | (fe && atoi(fe) == 0 ? 2 : 0) | radix_or_rank();
         if (T == 4096) {
-            if (f && g) k_radix_scatter<V, true, true, 4096><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar);
-            else if (f) k_radix_scatter<V, true, false, 4096><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar);
-            else if (g) k_radix_scatter<V, false, true, 4096><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar);
-            else k_radix_scatter<V, false, false, 4096><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar);
-        } else if (f && g) k_radix_scatter<V, true, true><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar);
-        else if (f) k_radix_scatter<V, true, false><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar);
-        else if (g) k_radix_scatter<V, false, true><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar);
-        else k_radix_scatter<V, false, false><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar);
+            if (f && g) k_radix_scatter<V, true, true, 4096><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar, o32);
+            else if (f) k_radix_scatter<V, true, false, 4096><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar, o32);
+            else if (g) k_radix_scatter<V, false, true, 4096><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar, o32);
+            else k_radix_scatter<V, false, false, 4096><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar, o32);
+        } else if (f && g) k_radix_scatter<V, true, true><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar, o32);
+        else if (f) k_radix_scatter<V, true, false><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar, o32);
+        else if (g) k_radix_scatter<V, false, true><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar, o32);
+        else k_radix_scatter<V, false, false><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar, o32);
         std::swap(di, dg);
         if (f) {
-            uint64_t kept = 0;
-            hipMemcpyAsync(&kept, offs + 256ull * nTiles, sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+            uint64_t kept = 0;  // little-endian host: a 4-B total lands in the low word
+            if (o32) hipMemcpyAsync(&kept, reinterpret_cast<uint32_t*>(offs) + 256ull * nTiles, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+            else hipMemcpyAsync(&kept, offs + 256ull * nTiles, sizeof(uint64_t), hipMemcpyDeviceToHost, s);
             hipStreamSynchronize(s);
             cur = kept;
         }
@@ -946,12 +1024,14 @@ uint64_t radix_sort_binned(uint64_t* keysR, V* valsR, uint64_t* keysT, V* valsT,
     const int shift = bitLo + 8, ns = shift + 8;
     if (digR) k_radix_hist_dig<<<nTiles, kBlock, 0, s>>>(digR, 0, counts, nTiles, tileTab);
     else k_radix_hist<false><<<nTiles, kBlock, 0, s>>>(keysR, 0, shift, counts, nTiles, tileTab);  // no K1F digits
-    exclusive_scan_u32(counts, 256ull * nTiles, offs, scanTmp, s);
+    const int o32 = Q < (1ull << 32);
+    if (o32) exclusive_scan_u32_out32(counts, 256ull * nTiles, reinterpret_cast<uint32_t*>(offs), scanTmp, s);
+    else exclusive_scan_u32(counts, 256ull * nTiles, offs, scanTmp, s);
     const char* xe = getenv("MTB_RADIX_XCD");
     const int xcd = xe ? atoi(xe) : 1;
     k_radix_scatter<V, false, false><<<nTiles, kBlock, 0, s>>>(keysR, valsR, 0, shift, offs, nTiles, keysT, valsT,
                                                               ns < bitHi ? digT : nullptr, ns, xcd, tileTab,
-                                                              radix_or_rank());
+                                                              radix_or_rank(), o32);
     *inT = true;
     if (ns < bitHi) {  // the rest: plain passes over the Q contiguous pairs
         bool inB = false;

@@ -83,6 +83,8 @@ inline unsigned stride_grid(uint64_t n, unsigned block = 256) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
 void exclusive_scan_u32(const uint32_t* in, uint64_t n, uint64_t* out, void* tmp, hipStream_t s);
 void exclusive_scan_u64(const uint64_t* in, uint64_t n, uint64_t* out, void* tmp, hipStream_t s);
+// the same scan with 4-B outputs, for a caller whose total is below 2^32 (sums past it are truncated)
+void exclusive_scan_u32_out32(const uint32_t* in, uint64_t n, uint32_t* out, void* tmp, hipStream_t s);
 // K6 run index from the flag bytes of launch_run_flags and the scans of its per-read counts
 // (grpOff / runOff, n + 1): gStart (groups + 1), sStart and runGroup (runs + 1)
 void launch_run_starts(const uint8_t* flags, const uint64_t* mOff, const uint64_t* grpOff, const uint64_t* runOff,
