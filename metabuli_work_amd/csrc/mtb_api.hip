@@ -2372,7 +2372,8 @@ extern "C" int mtb_pin_eval(int device, int fn, const int64_t* param, const uint
 
 // K2 alone (staged entry): the (key, 32-bit value) pairs sorted on key bits [bit_lo, bit_hi) by the
 // LSD radix sort the query sort runs (radix_sort_pairs: every pass stable, with the knobs it reads —
-// MTB_RADIX_ORRANK, MTB_RADIX_TILE, MTB_RADIX_FULLTILE, MTB_RADIX_XCD), 8-bit digits. Host arrays.
+// MTB_RADIX_ORRANK, MTB_RADIX_TILE, MTB_RADIX_FULLTILE, MTB_RADIX_XCD, MTB_RADIX_THREADS), 8-bit digits.
+// Host arrays.
 extern "C" int mtb_sort_pairs(int device, const uint64_t* keys, const uint32_t* vals, uint64_t n, int bit_lo,
                               int bit_hi, uint64_t* keys_out, uint32_t* vals_out) {
     if (n && (!keys || !vals || !keys_out || !vals_out)) { set_error("null argument"); return MTB_ERR_ARG; }

@@ -4,6 +4,7 @@
 #include "mtb_launch.h"
 
 #include <cstring>
+#include <type_traits>
 
 namespace mtb {
 
@@ -24,15 +25,16 @@ __device__ __forceinline__ unsigned long long wave_inclusive_scan(unsigned long 
 }
 
 // Exclusive scan over the block; returns the exclusive prefix of x, *total = block sum.
+template <int WAVES = kWaves>
 __device__ __forceinline__ unsigned long long block_exclusive_scan(unsigned long long x, unsigned long long* total) {
-    __shared__ unsigned long long wsum[kWaves];
+    __shared__ unsigned long long wsum[WAVES];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     unsigned long long inc = wave_inclusive_scan(x);
     if (lane == 63) wsum[w] = inc;
     __syncthreads();
     unsigned long long off = 0, tot = 0;
 #pragma unroll
-    for (int i = 0; i < kWaves; i++) {
+    for (int i = 0; i < WAVES; i++) {
         if (i < w) off += wsum[i];
         tot += wsum[i];
     }
@@ -249,35 +251,57 @@ void exclusive_scan_u64(const uint64_t* in, uint64_t n, uint64_t* out, void* tmp
 // pair dropped by the empty rule adds nothing to maxW[0] whatever its other mate's length, so a batch
 // can be uniform and still hold a mate that K1F's LDS stage has no room for (launch_extract_filter).
 // ------------------------------------------------------------------------------------------------
-__global__ void k_read_meta(const uint64_t* __restrict__ off1, const uint64_t* __restrict__ off2, uint32_t n,
+// A block takes kMetaReads consecutive reads per thread (stretch q = its reads [q * kBlock, (q + 1) *
+// kBlock), thread t read t of each: coalesced) and reduces the two maxima over its waves and LDS, so
+// one thread issues at most two atomicMax per block and none for a zero: an atomic per read with a
+// window made the batch's 52k wave-level atomics on one word the kernel's whole time.
+constexpr int kMetaReads = 4;
+__global__ void __launch_bounds__(kBlock) k_read_meta(const uint64_t* __restrict__ off1, const uint64_t* __restrict__ off2, uint32_t n,
                             int paired, ReadMeta* __restrict__ meta, uint32_t* __restrict__ qlen,
                             uint32_t* __restrict__ maxW, uint32_t* __restrict__ readLens) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int len1 = (int)(off1[i + 1] - off1[i]);
-    int ql1 = max_covered_length(len1);
-    int w1 = query_kmer_number(len1) / 6;  // windows per frame (KmerExtractor.cpp:462,481)
-    int len2 = 0, ql2 = 0, w2 = 0;
-    bool empty = w1 < 1;
-    if (paired) {
-        len2 = (int)(off2[i + 1] - off2[i]);
-        ql2 = max_covered_length(len2);
-        w2 = query_kmer_number(len2) / 6;
-        if (w2 < 1) empty = true;
+    __shared__ uint32_t sMax[2][kWaves];
+    uint32_t w = 0, big = 0;
+#pragma unroll
+    for (int q = 0; q < kMetaReads; q++) {
+        const uint64_t i = ((uint64_t)blockIdx.x * kMetaReads + q) * kBlock + threadIdx.x;
+        if (i >= n) break;
+        int len1 = (int)(off1[i + 1] - off1[i]);
+        int ql1 = max_covered_length(len1);
+        int w1 = query_kmer_number(len1) / 6;  // windows per frame (KmerExtractor.cpp:462,481)
+        int len2 = 0, ql2 = 0, w2 = 0;
+        bool empty = w1 < 1;
+        if (paired) {
+            len2 = (int)(off2[i + 1] - off2[i]);
+            ql2 = max_covered_length(len2);
+            w2 = query_kmer_number(len2) / 6;
+            if (w2 < 1) empty = true;
+        }
+        ReadMeta m;
+        m.len1 = len1; m.len2 = len2; m.ql1 = ql1; m.ql2 = ql2;
+        m.w1 = empty ? 0 : w1;
+        m.w2 = (empty || !paired) ? 0 : w2;
+        meta[i] = m;
+        qlen[i] = (uint32_t)(ql1 + ql2);
+        // the mates' lengths in 16 bits each (K4 rebuilds a uniform unit's info from them; read only when
+        // every frame is one chunk, i.e. reads of a few hundred bases)
+        readLens[i] = (uint32_t)min(len1, 0xFFFF) | (uint32_t)min(len2, 0xFFFF) << 16;
+        w = max(w, (uint32_t)max(m.w1, m.w2));
+        const uint32_t longer = (uint32_t)max(len1, len2);
+        if (longer > kSeqMate) big = max(big, longer);
     }
-    ReadMeta m;
-    m.len1 = len1; m.len2 = len2; m.ql1 = ql1; m.ql2 = ql2;
-    m.w1 = empty ? 0 : w1;
-    m.w2 = (empty || !paired) ? 0 : w2;
-    meta[i] = m;
-    qlen[i] = (uint32_t)(ql1 + ql2);
-    // the mates' lengths in 16 bits each (K4 rebuilds a uniform unit's info from them; read only when
-    // every frame is one chunk, i.e. reads of a few hundred bases)
-    readLens[i] = (uint32_t)min(len1, 0xFFFF) | (uint32_t)min(len2, 0xFFFF) << 16;
-    const uint32_t w = (uint32_t)max(m.w1, m.w2);
-    if (w) atomicMax(maxW, w);
-    const uint32_t big = (uint32_t)max(len1, len2);
-    if (big > kSeqMate) atomicMax(maxW + 1, big);
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+        w = max(w, (uint32_t)__shfl_xor((int)w, d, 64));
+        big = max(big, (uint32_t)__shfl_xor((int)big, d, 64));
+    }
+    if ((threadIdx.x & 63) == 0) { sMax[0][threadIdx.x >> 6] = w; sMax[1][threadIdx.x >> 6] = big; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int x = 1; x < kWaves; x++) { w = max(w, sMax[0][x]); big = max(big, sMax[1][x]); }
+        if (w) atomicMax(maxW, w);
+        if (big) atomicMax(maxW + 1, big);
+    }
 }
 
 // K1 work units per read: each (mate, frame) is cut into chunks of C windows. Uniform units (upr > 0:
@@ -302,7 +326,7 @@ void launch_read_meta(const uint64_t* off1, const uint64_t* off2, uint32_t n, in
                       uint32_t* qlen, uint32_t* maxW, uint32_t* readLens, hipStream_t s) {
     hipMemsetAsync(maxW, 0, 2 * sizeof(uint32_t), s);
     if (n == 0) return;
-    k_read_meta<<<(n + 255) / 256, 256, 0, s>>>(off1, off2, n, paired, meta, qlen, maxW, readLens);
+    k_read_meta<<<(unsigned)(((uint64_t)n + kMetaReads * kBlock - 1) / (kMetaReads * kBlock)), kBlock, 0, s>>>(off1, off2, n, paired, meta, qlen, maxW, readLens);
 }
 
 void launch_read_units(const ReadMeta* meta, uint32_t n, uint32_t C, uint32_t upr, uint32_t* units, hipStream_t s) {
@@ -596,7 +620,7 @@ void launch_extract(const uint8_t* seq1, const uint64_t* off1, const uint8_t* se
 // K2 LSD radix sort of (key, val) pairs on 8-bit digits of the key. Per pass: tile histograms
 // (digit-major so one device scan yields stable global offsets), scan, stable scatter through an
 // LDS-staged tile so each digit run leaves the block as one contiguous write. Each wave ranks its
-// own 2048-key slice against a wave-private histogram (from per-digit lane masks, or match-any
+// own 2048-key slice (1024 keys on 512 threads, the query sort's form) against a wave-private histogram (from per-digit lane masks, or match-any
 // ballots), so the tile needs two block barriers per pass rather than several per 256 keys. The first pass (FILTER) drops
 // sentinel keys: the compaction of blank reserved slots costs nothing extra.
 // ------------------------------------------------------------------------------------------------
@@ -695,17 +719,24 @@ __global__ void __launch_bounds__(256) k_radix_hist_dig(const uint8_t* __restric
 // V: value type (64-bit payloads, or 32-bit slot indices). GEN: the values are the input positions
 // (the first pass of a sort of slots), so none are read. digOut (nullable): the next pass's digit
 // (bits [nextShift, nextShift + 8) of the key) of every written key, at its output position.
-template <typename V, bool FILTER, bool GEN, int TILE = kRadixTile>
-__global__ void __launch_bounds__(256) k_radix_scatter(const uint64_t* __restrict__ keysIn, const V* __restrict__ valsIn,
+// THREADS: 256 (32 keys per lane of an 8192-key tile), or 512 (16 per lane: the same tile, histograms,
+// scans and digit runs, half the ranking chain per wave; held to 128 VGPRs so that the two blocks the
+// LDS allows are 4 waves per SIMD instead of 2). Wave w ranks the tile's keys [w * kSlice, (w + 1) *
+// kSlice) in input order and the waves are placed in w order, so both forms write the same bytes. With
+// eight waves the wave histograms are 16-bit (a wave's digit count is at most 1024, a tile position
+// at most 8192) to keep the block under half the CU's LDS; that form has no atomicRank & 1 path.
+template <typename V, bool FILTER, bool GEN, int TILE = kRadixTile, int THREADS = kBlock>
+__global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS == 512 ? 4 : 1))) k_radix_scatter(const uint64_t* __restrict__ keysIn, const V* __restrict__ valsIn,
                                                        uint64_t n, int shift, const uint64_t* __restrict__ offs,
                                                        uint32_t nTiles, uint64_t* __restrict__ keysOut,
                                                        V* __restrict__ valsOut, uint8_t* __restrict__ digOut,
                                                        int nextShift, int xcdMap, const uint64_t* __restrict__ tab,
                                                        int atomicRank, int offs32) {
-    constexpr int kItems = TILE / kBlock, kSlice = 64 * kItems;
+    constexpr int kItems = TILE / THREADS, kWaves = THREADS / 64, kSlice = 64 * kItems;
+    using H = std::conditional_t<THREADS == 512, uint16_t, uint32_t>;
     __shared__ uint64_t sKV[TILE];  // keys, then (after they are written out) values
     __shared__ uint8_t sDig[TILE];
-    __shared__ uint32_t waveHist[kWaves][256];
+    __shared__ H waveHist[kWaves][256];
     __shared__ uint64_t sDst[256];  // global slot of this tile's first key of digit d, minus its tile offset
     __shared__ uint32_t sKept;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -726,11 +757,13 @@ __global__ void __launch_bounds__(256) k_radix_scatter(const uint64_t* __restric
     // the digit bases: one strided load per lane, issued first so its latency hides behind the
     // key loads (a dependent load per key in the write-out loop was the old bottleneck)
     // offs32: the scan wrote 4-B offsets (a sort of fewer than 2^32 pairs): half the bytes of this gather
-    const uint64_t digitBase = offs32 ? reinterpret_cast<const uint32_t*>(offs)[(uint64_t)tid * nTiles + tile]
-                                      : offs[(uint64_t)tid * nTiles + tile];
-    for (int x = tid; x < kWaves * 256; x += kBlock) (&waveHist[0][0])[x] = 0;
+    uint64_t digitBase = 0;
+    if (THREADS == 256 || tid < 256)
+        digitBase = offs32 ? reinterpret_cast<const uint32_t*>(offs)[(uint64_t)tid * nTiles + tile]
+                           : offs[(uint64_t)tid * nTiles + tile];
+    for (int x = tid; x < kWaves * 256; x += THREADS) (&waveHist[0][0])[x] = 0;
     if (atomicRank & 4)
-        for (int x = tid; x < kWaves * 256; x += kBlock) sKV[x] = 0;  // the digits' lane masks (below)
+        for (int x = tid; x < kWaves * 256; x += THREADS) sKV[x] = 0;  // the digits' lane masks (below)
     __syncthreads();
 
     const unsigned long long ltMask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
@@ -761,13 +794,15 @@ __global__ void __launch_bounds__(256) k_radix_scatter(const uint64_t* __restric
     // first pass alone measured even (ab_radixatomic_first.json): off by default (MTB_RADIX_ATOMIC_FIRST).
     // atomicRank & 4 (the default): the lane-mask ranking below, stable by construction, in place of the
     // nine ballots (sort 14.8 -> 14.2-14.3 ms same box, profiles/r05/ab_radix_orrank.json)
-    if (atomicRank & 1) {
+    if (sizeof(H) == 4 && (atomicRank & 1)) {
+        if constexpr (sizeof(H) == 4) {
 #pragma unroll
-        for (int r = 0; r < kItems; r++) {
-            const uint64_t i = base + (uint64_t)r * 64 + lane;
-            const bool valid = i < n && (!FILTER || k[r] != kSentinel);
-            const uint32_t d = valid ? radix_digit(k[r], shift) : 0u;
-            rk[r] = valid ? (d << 16 | atomicAdd(&waveHist[w][d], 1u)) : ~0u;
+            for (int r = 0; r < kItems; r++) {
+                const uint64_t i = base + (uint64_t)r * 64 + lane;
+                const bool valid = i < n && (!FILTER || k[r] != kSentinel);
+                const uint32_t d = valid ? radix_digit(k[r], shift) : 0u;
+                rk[r] = valid ? (d << 16 | atomicAdd(&waveHist[w][d], 1u)) : ~0u;
+            }
         }
     } else if (atomicRank & 4) {
         // stable ranking from each digit's lane mask (sKV holds the masks until the keys are staged):
@@ -786,7 +821,7 @@ __global__ void __launch_bounds__(256) k_radix_scatter(const uint64_t* __restric
                 const uint32_t before = waveHist[w][d];
                 const uint32_t rankInWave = (uint32_t)__popcll(peers & ltMask);
                 if (rankInWave == 0) {
-                    waveHist[w][d] = before + (uint32_t)__popcll(peers);
+                    waveHist[w][d] = (H)(before + (uint32_t)__popcll(peers));
                     __hip_atomic_store(&sMask[d], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
                 rk[r] = d << 16 | (before + rankInWave);
@@ -803,7 +838,7 @@ __global__ void __launch_bounds__(256) k_radix_scatter(const uint64_t* __restric
             const uint32_t before = valid ? waveHist[w][d] : 0u;
             const uint32_t rankInWave = (uint32_t)__popcll(peers & ltMask);
             if (valid && rankInWave == 0) {
-                waveHist[w][d] = before + (uint32_t)__popcll(peers);
+                waveHist[w][d] = (H)(before + (uint32_t)__popcll(peers));
                 __hip_atomic_store(&sMask[d], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
             rk[r] = valid ? (d << 16 | (before + rankInWave)) : ~0u;
@@ -822,7 +857,7 @@ __global__ void __launch_bounds__(256) k_radix_scatter(const uint64_t* __restric
             }
             const uint32_t before = waveHist[w][d];
             const uint32_t rankInWave = (uint32_t)__popcll(peers & ltMask);
-            if (rankInWave == 0) waveHist[w][d] = before + (uint32_t)__popcll(peers);
+            if (rankInWave == 0) waveHist[w][d] = (H)(before + (uint32_t)__popcll(peers));
             rk[r] = d << 16 | (before + rankInWave);
         }
     } else
@@ -841,21 +876,25 @@ __global__ void __launch_bounds__(256) k_radix_scatter(const uint64_t* __restric
         // operations of one wave complete in program order
         const uint32_t before = valid ? waveHist[w][d] : 0u;
         const uint32_t rankInWave = (uint32_t)__popcll(peers & ltMask);
-        if (valid && rankInWave == 0) waveHist[w][d] = before + (uint32_t)__popcll(peers);
+        if (valid && rankInWave == 0) waveHist[w][d] = (H)(before + (uint32_t)__popcll(peers));
         rk[r] = valid ? (d << 16 | (before + rankInWave)) : ~0u;
     }
     __syncthreads();
     {
+        // digit tid's counts over the waves (512 threads: the upper half only takes part in the scan)
+        const bool own = THREADS == 256 || tid < 256;
         uint32_t c[kWaves], sum = 0;
 #pragma unroll
-        for (int ww = 0; ww < kWaves; ww++) { c[ww] = waveHist[ww][tid]; sum += c[ww]; }
+        for (int ww = 0; ww < kWaves; ww++) { c[ww] = own ? waveHist[ww][tid & 255] : 0u; sum += c[ww]; }
         unsigned long long tot;
-        const uint32_t start = (uint32_t)block_exclusive_scan(sum, &tot);
-        sDst[tid] = digitBase - start;
+        const uint32_t start = (uint32_t)block_exclusive_scan<kWaves>(sum, &tot);
+        if (own) sDst[tid] = digitBase - start;
         if (tid == 0) sKept = (uint32_t)tot;
         uint32_t run = start;
+        if (own) {
 #pragma unroll
-        for (int ww = 0; ww < kWaves; ww++) { waveHist[ww][tid] = run; run += c[ww]; }
+            for (int ww = 0; ww < kWaves; ww++) { waveHist[ww][tid] = (H)run; run += c[ww]; }
+        }
     }
     __syncthreads();
     // keys and values go through one LDS tile in two rounds (half the LDS of staging both, so
@@ -870,13 +909,13 @@ __global__ void __launch_bounds__(256) k_radix_scatter(const uint64_t* __restric
     }
     __syncthreads();
     if (digOut) {
-        for (uint32_t i = tid; i < sKept; i += kBlock) {
+        for (uint32_t i = tid; i < sKept; i += THREADS) {
             const uint64_t o = sDst[sDig[i]] + i;
             keysOut[o] = sKV[i];
             digOut[o] = (uint8_t)radix_digit(sKV[i], nextShift);
         }
     } else {
-        for (uint32_t i = tid; i < sKept; i += kBlock) keysOut[sDst[sDig[i]] + i] = sKV[i];
+        for (uint32_t i = tid; i < sKept; i += THREADS) keysOut[sDst[sDig[i]] + i] = sKV[i];
     }
     __syncthreads();
     V* sV = reinterpret_cast<V*>(sKV);
@@ -884,7 +923,7 @@ __global__ void __launch_bounds__(256) k_radix_scatter(const uint64_t* __restric
     for (int r = 0; r < kItems; r++)
         if (rk[r] != ~0u) sV[rk[r]] = v[r];
     __syncthreads();
-    for (uint32_t i = tid; i < sKept; i += kBlock) valsOut[sDst[sDig[i]] + i] = sV[i];
+    for (uint32_t i = tid; i < sKept; i += THREADS) valsOut[sDst[sDig[i]] + i] = sV[i];
 }
 
 // sized for the smallest tile radix_sort_pairs may take (MTB_RADIX_TILE=4096)
@@ -906,6 +945,14 @@ static uint32_t radix_tile() {
 static int radix_or_rank() {
     const char* e = getenv("MTB_RADIX_ORRANK");
     return !e || atoi(e) ? 4 : 0;
+}
+
+// MTB_RADIX_THREADS=256 (A/B and tests, read per sort): the 256-thread scatter for every pass. Default
+// 512: the passes of a sort of 32-bit values over 8192-key tiles without filter or generated values
+// (the query sort's three) run the 512-thread form; every other pass is 256 threads either way.
+static uint32_t radix_threads() {
+    const char* e = getenv("MTB_RADIX_THREADS");
+    return e && atoi(e) == 256 ? 256u : 512u;
 }
 
 template <typename V>
@@ -943,7 +990,13 @@ uint64_t radix_sort_pairs(uint64_t* keysA, V* valsA, uint64_t* keysB, V* valsB, 
         // MTB_RADIX_FULLTILE=0 (A/B, read per sort): full tiles ranked by the general path too
         const char* fe = getenv("MTB_RADIX_FULLTILE");
         const int ar = (first && unstableFirst ? 1 : 0) | (fe && atoi(fe) == 0 ? 2 : 0) | radix_or_rank();
-        if (T == 4096) {
+        bool wide = false;  // the query sort's passes: the 512-thread form (radix_threads), the only one measured
+        if constexpr (sizeof(V) == 4) {
+            wide = T == kRadixTile && !f && !g && !(ar & 1) && radix_threads() == 512;
+            if (wide) k_radix_scatter<V, false, false, kRadixTile, 512><<<nTiles, 512, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar, o32);
+        }
+        if (wide) {  // launched above
+        } else if (T == 4096) {
             if (f && g) k_radix_scatter<V, true, true, 4096><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar, o32);
             else if (f) k_radix_scatter<V, true, false, 4096><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar, o32);
             else if (g) k_radix_scatter<V, false, true, 4096><<<nTiles, kBlock, 0, s>>>(ki, vi, cur, shift, offs, nTiles, ko, vo, dOut, ns, xcd, nullptr, ar, o32);
