@@ -18,8 +18,8 @@ reads whose taxCnt overflows K6's LDS hashes (65 and 257 distinct taxa).
 compareDna on the device: no test here. The device's selection in K4 stays covered by
 test_gpu_parity.test_stage_parity, now against a pinned oracle.
 
-Still unpinned: the matchKmers merge loop (KmerMatcher.cpp:251-450) and MMseqs2's taxonomy services
-(LCA, IsAncestor, rank lookup), which the fixture's generator replaces with plain parent walks.
+Still unpinned: MMseqs2's taxonomy services (LCA, IsAncestor, rank lookup), which the fixture's generator
+replaces with plain parent walks. The matchKmers merge loop is pinned in test_ref_match.py.
 """
 import ctypes
 import os
