@@ -565,6 +565,85 @@ int mtb_em(mtb_ctx* ctx, const mtb_em_map* maps, uint64_t n_maps, uint64_t total
 int mtb_write_em_results(mtb_ctx* ctx, const char* path, const char* classification_tsv, const mtb_em_read* reads,
                          uint64_t n_reads, uint32_t flags);
 
+/* ---- read grouping (the fork's src/read-group/, workflow groupGeneration) ------------------------
+ * Reads that share AA 12-mers are linked (edge weight = shared k-mers) and grouped by union-find in
+ * three phases; groupMap[i] is the smallest read ID of read i's group, 0 for an ungrouped read.
+ * Read IDs are 1-based over the whole run (writeKmers, GroupGenerator.cpp:449). */
+typedef struct mtb_group_params { /* setGroupGenerationDefaults, groupGeneration.cpp:9-58 */
+    int32_t seq_mode;             /* 1 single-end, 2 paired-end, 3 long reads                      */
+    int32_t syncmer;              /* 1: kmerFormat 5 (closed syncmers), 0: kmerFormat 3            */
+    int32_t smer_len;             /* s-mer length (5)                                              */
+    int32_t max_kmer_reads;       /* --max-kmer-reads (1000): k-mers held by more reads are skipped */
+    float max_kmer_quantile;      /* cap from the reads-per-k-mer histogram when max_kmer_reads = 0 */
+    float min_overlap_ratio;      /* core threshold = ratio x k-mers per read (0.3)                */
+    float weak_band_ratio;        /* weak threshold = ratio x core threshold (0.3333)              */
+    float merge_support_ratio;    /* must be 0 (MTB_ERR_UNSUPPORTED otherwise: merge-order dependent) */
+    int32_t merge_max_unit_reads; /* must be 0 (likewise)                                          */
+    int32_t reserved;
+} mtb_group_params;
+/* Relation (GroupGenerator.h:39-75), 12 B, pad 0 as makeRelation writes it; id1 < id2. */
+typedef struct mtb_relation {
+    uint32_t id1, id2;
+    uint16_t weight, pad;
+} mtb_relation;
+/* ms: device time per stage — [5] Phase 1, [6] Phase 1.5, [7] Phase 2 ([0]..[4]: the edge build's
+ * stages; 0 from mtb_group_make_groups). groups_after / grouped_after: groups and grouped reads in
+ * the groupMap after each of the three phases. */
+typedef struct mtb_group_stats {
+    uint64_t reads, kmers, distinct_kmers, skipped_kmers, kept_pair_occurrences, edges, rounds, cap;
+    uint64_t hist_kmers[64], hist_pairs[64], groups_after[3], grouped_after[3];
+    int32_t core_thr, weak_thr;
+    float ms[8];
+} mtb_group_stats;
+void mtb_group_default_params(mtb_group_params* par);
+
+/* A grouping run on one device: batches of reads in, the shared-k-mer graph and the groupMap out.
+ * Everything stays resident in HBM (no kmer_delta_* / subGraph_* spill). Out of scope: the common-k-mer
+ * filter (the graph is over all extracted k-mers, and total k-mers is their count), masking,
+ * mergeGraph_one, GroupApplier, more than one GPU. */
+typedef struct mtb_grouper mtb_grouper;
+int mtb_group_open(const mtb_group_params* par, int device, mtb_grouper** out);
+void mtb_group_close(mtb_grouper* g);
+/* Extracts the batch's AA 12-mers (fillQueryKmerBuffer with KmerScanner_dna2aa(12), or with syncmer
+ * SyncmerScanner_dna2aa(12, smer_len): 60-bit values, all six frames, mate 2 under mate 1's read ID)
+ * and appends them to the run's. Layout as mtb_classify_batch's (MTB_INPUT_DEVICE: device pointers);
+ * read IDs continue from the earlier batches (1-based over the run). A pair one of whose mates holds
+ * no 12-mer emits nothing (the shared empty-read rule). */
+int mtb_group_add_batch(mtb_grouper* g, const char* seq, const uint64_t* off, const char* seq2,
+                        const uint64_t* off2, uint32_t n_reads, uint32_t flags);
+/* Staged: the k-mer instances so far (value, read ID), in emission order before mtb_group_build_edges,
+ * sorted by value after. MTB_RETRY (n set) when cap is too small. */
+int mtb_group_get_kmers(mtb_grouper* g, uint64_t* values, uint32_t* read_ids, uint64_t cap, uint64_t* n);
+/* makeSubGraph + mergeGraph (GroupGenerator.cpp:649-701, GroupGenerator.h:756-808): per distinct k-mer
+ * the distinct reads holding it (m); histograms of the k-mers with m >= 2 by floor(log2 m) (k-mers and
+ * C(m,2)); cap = max_kmer_reads if > 0, else the quantile's cap (capFromQuantile) when
+ * max_kmer_quantile is inside (0, 1), else 0 = off; a k-mer with m > cap > 0 is skipped; every other
+ * adds 1 to the weight of each pair of its reads; weights saturate at 65535. Pairs are emitted in
+ * rounds of at most pair_budget (0: from free HBM), one thread per pair; a budget below the largest
+ * kept clique is MTB_ERR_ARG; MTB_ERR_OOM (the bytes needed in mtb_last_error) when the graph does
+ * not fit the device. May be called again (another budget); no batch may follow it.
+ * stats->ms: [0] extraction (all batches), [1] k-mer sort, [2] run pass, [3] pair rounds (emit, sort,
+ * reduce), [4] cross-round merge and records. */
+int mtb_group_build_edges(mtb_grouper* g, uint64_t pair_budget, mtb_group_stats* stats);
+/* The edges, (id1, id2) ascending; MTB_RETRY (n set) when cap is too small. */
+int mtb_group_get_edges(mtb_grouper* g, mtb_relation* out, uint64_t cap, uint64_t* n);
+/* The skipped k-mers (value, m), value ascending (the reference logs them as "value \t m"). */
+int mtb_group_get_skipped(mtb_grouper* g, uint64_t* values, uint32_t* m, uint64_t cap, uint64_t* n);
+/* The three phases on the resident edges, total k-mers = the instances extracted; group_map: reads + 1
+ * entries (entry 0 unused). Reads without a k-mer get label 0. */
+int mtb_group_finish(mtb_grouper* g, uint32_t* group_map, mtb_group_stats* stats);
+
+/* The three phases alone on host edges over reads 1 .. n_reads (makeGroups, mergeBySupport at its
+ * defaults, makeGroupsPhase2: GroupGenerator.cpp:1469-2053). Thresholds as GroupGenerator.cpp:171-192
+ * forms them: coreThr = int(min_overlap_ratio x total_kmers / n_reads + 0.5), weakThr =
+ * int(weak_band_ratio x coreThr + 0.5f) clamped to [1, coreThr - 1]. phase_maps: 3 x (n_reads + 1)
+ * entries, the groupMap after Phase 1, 1.5 and 2 (entry 0 of each unused, 0). MTB_ERR_ARG: coreThr < 2,
+ * 2^32 - 1 reads or more, a ratio outside its range; MTB_ERR_UNSUPPORTED: a positive
+ * merge_support_ratio or merge_max_unit_reads. */
+int mtb_group_make_groups(int device, const mtb_relation* edges, uint64_t n_edges, uint32_t n_reads,
+                          uint64_t total_kmers, const mtb_group_params* par, uint32_t* phase_maps,
+                          mtb_group_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

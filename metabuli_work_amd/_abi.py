@@ -126,3 +126,25 @@ EM_READ_DTYPE = np.dtype([("tax_id", "<i4"), ("mapped", "<i4"), ("score", "<f8")
 class MtbEmStats(ctypes.Structure):
     _fields_ = [("query_count", ctypes.c_uint64), ("iterations", ctypes.c_uint32), ("n_species", ctypes.c_uint32),
                 ("delta", ctypes.c_double)]
+
+
+# read grouping (include/mtb_gpu.h: mtb_group_params, mtb_relation, mtb_group_stats)
+class MtbGroupParams(ctypes.Structure):
+    _fields_ = [("seq_mode", ctypes.c_int32), ("syncmer", ctypes.c_int32), ("smer_len", ctypes.c_int32),
+                ("max_kmer_reads", ctypes.c_int32), ("max_kmer_quantile", ctypes.c_float),
+                ("min_overlap_ratio", ctypes.c_float), ("weak_band_ratio", ctypes.c_float),
+                ("merge_support_ratio", ctypes.c_float), ("merge_max_unit_reads", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class MtbGroupStats(ctypes.Structure):
+    _fields_ = [("reads", ctypes.c_uint64), ("kmers", ctypes.c_uint64), ("distinct_kmers", ctypes.c_uint64),
+                ("skipped_kmers", ctypes.c_uint64), ("kept_pair_occurrences", ctypes.c_uint64),
+                ("edges", ctypes.c_uint64), ("rounds", ctypes.c_uint64), ("cap", ctypes.c_uint64),
+                ("hist_kmers", ctypes.c_uint64 * 64), ("hist_pairs", ctypes.c_uint64 * 64),
+                ("groups_after", ctypes.c_uint64 * 3), ("grouped_after", ctypes.c_uint64 * 3),
+                ("core_thr", ctypes.c_int32), ("weak_thr", ctypes.c_int32), ("ms", ctypes.c_float * 8)]
+
+
+RELATION_DTYPE = np.dtype([("id1", "<u4"), ("id2", "<u4"), ("weight", "<u2"), ("pad", "<u2")])
+assert RELATION_DTYPE.itemsize == 12

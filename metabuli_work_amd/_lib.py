@@ -7,7 +7,8 @@ entry point raises. Build it with `python -c "import __graft_entry__ as g; g.bui
 import ctypes
 import pathlib
 
-from ._abi import MtbClassifyOpts, MtbClassifyStats, MtbDbHost, MtbDbResident, MtbEmStats, MtbParams, MtbReadBatch
+from ._abi import (MtbClassifyOpts, MtbClassifyStats, MtbDbHost, MtbDbResident, MtbEmStats, MtbGroupParams, MtbGroupStats,
+                   MtbParams, MtbReadBatch)
 
 _HERE = pathlib.Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libmtbgpu.so"
@@ -26,6 +27,8 @@ EXPORTED = [
     "mtb_open_phases", "mtb_start_classify_partitioned", "mtb_release_workspace", "mtb_hamming", "mtb_memcpy",
     "mtb_line_ext_check", "mtb_link_check", "mtb_pin_eval", "mtb_sort_pairs", "mtb_sort_pairs64",
     "mtb_merge_db", "mtb_merge_db_dirs", "mtb_merge_last_ms", "mtb_merge_tile_items", "mtb_scan_u32",
+    "mtb_group_default_params", "mtb_group_make_groups", "mtb_group_open", "mtb_group_close", "mtb_group_add_batch",
+    "mtb_group_get_kmers", "mtb_group_build_edges", "mtb_group_get_edges", "mtb_group_get_skipped", "mtb_group_finish",
 ]
 
 
@@ -107,6 +110,18 @@ def lib() -> ctypes.CDLL:
     L.mtb_merge_last_ms.argtypes = [P(ctypes.c_float), i32]
     L.mtb_merge_tile_items.argtypes = []
     L.mtb_merge_tile_items.restype = u32
+    L.mtb_group_default_params.argtypes = [P(MtbGroupParams)]
+    L.mtb_group_default_params.restype = None
+    L.mtb_group_make_groups.argtypes = [i32, vp, u64, u32, u64, P(MtbGroupParams), vp, P(MtbGroupStats)]
+    L.mtb_group_open.argtypes = [P(MtbGroupParams), i32, P(vp)]
+    L.mtb_group_close.argtypes = [vp]
+    L.mtb_group_close.restype = None
+    L.mtb_group_add_batch.argtypes = [vp, vp, vp, vp, vp, u32, u32]
+    L.mtb_group_get_kmers.argtypes = [vp, vp, vp, u64, P(u64)]
+    L.mtb_group_build_edges.argtypes = [vp, u64, P(MtbGroupStats)]
+    L.mtb_group_get_edges.argtypes = [vp, vp, u64, P(u64)]
+    L.mtb_group_get_skipped.argtypes = [vp, vp, vp, u64, P(u64)]
+    L.mtb_group_finish.argtypes = [vp, vp, P(MtbGroupStats)]
     L.mtb_debug_tables.argtypes = [vp, vp, vp]
     L.mtb_debug_tables.restype = None
     _LIB = L

@@ -1,0 +1,227 @@
+"""Read grouping on the GPU (the reference fork's groupGeneration workflow): the binding of the
+mtb_group_* section of include/mtb_gpu.h.
+
+make_groups runs the three grouping phases (makeGroups, mergeBySupport at its defaults,
+makeGroupsPhase2) on an edge list and returns the groupMap after each phase.
+"""
+import ctypes
+import dataclasses
+
+import numpy as np
+
+from ._abi import RELATION_DTYPE, MtbGroupParams, MtbGroupStats
+from ._lib import check, lib
+
+
+@dataclasses.dataclass
+class GroupParams:
+    """setGroupGenerationDefaults (groupGeneration.cpp:9-58)."""
+    seq_mode: int = 2
+    syncmer: int = 1
+    smer_len: int = 5
+    max_kmer_reads: int = 1000
+    max_kmer_quantile: float = 0.0
+    min_overlap_ratio: float = 0.3
+    weak_band_ratio: float = 0.3333
+    merge_support_ratio: float = 0.0
+    merge_max_unit_reads: int = 0
+
+    def to_c(self) -> MtbGroupParams:
+        return MtbGroupParams(reserved=0, **dataclasses.asdict(self))
+
+    @classmethod
+    def defaults(cls) -> "GroupParams":
+        """The library's own defaults (mtb_group_default_params)."""
+        p = MtbGroupParams()
+        lib().mtb_group_default_params(ctypes.byref(p))
+        return cls(**{f.name: getattr(p, f.name) for f in dataclasses.fields(cls)})
+
+
+def stats_dict(st: MtbGroupStats) -> dict:
+    out = {}
+    for name, _ in MtbGroupStats._fields_:
+        v = getattr(st, name)
+        out[name] = list(v) if hasattr(v, "__len__") else v
+    return out
+
+
+def relations(id1, id2, weight) -> np.ndarray:
+    """An edge list as mtb_relation records (pad 0)."""
+    e = np.zeros(len(id1), RELATION_DTYPE)
+    e["id1"], e["id2"], e["weight"] = id1, id2, weight
+    return e
+
+
+def make_groups(edges: np.ndarray, n_reads: int, total_kmers: int, par: GroupParams = None, device: int = 0):
+    """The three phases on an edge list (RELATION_DTYPE). Returns (maps, stats): maps is a (3, n_reads + 1)
+    uint32 array, the groupMap after Phase 1, 1.5 and 2 (column 0 unused)."""
+    par = par or GroupParams()
+    edges = np.ascontiguousarray(edges, RELATION_DTYPE)
+    maps = np.zeros((3, n_reads + 1), np.uint32)
+    st = MtbGroupStats()
+    cp = par.to_c()
+    check(lib().mtb_group_make_groups(device, edges.ctypes.data if len(edges) else None, len(edges), n_reads,
+                                      total_kmers, ctypes.byref(cp), maps.ctypes.data, ctypes.byref(st)),
+          "mtb_group_make_groups")
+    return maps, stats_dict(st)
+
+
+def write_group_files(out_dir, group_map: np.ndarray) -> None:
+    """saveGroupsToFile (GroupGenerator.cpp:2055-2090): groupMap ("i \\t groupId" per read) and groups
+    (one line per group: the ID, then its members, each followed by a tab), groups and members ascending."""
+    import pathlib
+
+    out = pathlib.Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    gm = np.asarray(group_map, np.uint32)
+    n = len(gm) - 1
+    with open(out / "groupMap", "wb") as f:
+        ids = np.arange(1, n + 1)
+        f.write("".join(f"{i}\t{g}\n" for i, g in zip(ids.tolist(), gm[1:].tolist())).encode())
+    members = np.nonzero(gm[1:])[0] + 1
+    order = np.lexsort((members, gm[members]))
+    members = members[order]
+    labels = gm[members]
+    with open(out / "groups", "wb") as f:
+        start = 0
+        lines = []
+        bounds = np.nonzero(np.diff(labels))[0] + 1 if len(labels) else np.array([], np.int64)
+        for end in list(bounds) + ([len(labels)] if len(labels) else []):
+            lines.append(f"{labels[start]}\t" + "".join(f"{m}\t" for m in members[start:end].tolist()) + "\n")
+            start = end
+        f.write("".join(lines).encode())
+
+
+def _flat(reads):
+    """Concatenated bases and n + 1 offsets of a list of str / bytes reads."""
+    bs = [r.encode() if isinstance(r, str) else bytes(r) for r in reads]
+    off = np.zeros(len(bs) + 1, np.uint64)
+    off[1:] = np.cumsum([len(b) for b in bs], dtype=np.uint64)
+    seq = np.frombuffer(b"".join(bs) or b"\0", np.uint8).copy()
+    return seq, off
+
+
+class ReadGrouper:
+    """One grouping run on a device (mtb_grouper): add_batch ... build_edges, edges / skipped, finish."""
+
+    def __init__(self, par: GroupParams = None, device: int = 0):
+        self.par = par or GroupParams()
+        self._h = ctypes.c_void_p()
+        cp = self.par.to_c()
+        check(lib().mtb_group_open(ctypes.byref(cp), device, ctypes.byref(self._h)), "mtb_group_open")
+        self.reads = 0
+        self.stats = None
+
+    def close(self):
+        if self._h:
+            lib().mtb_group_close(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def add_batch(self, seq1, off1, seq2=None, off2=None, flags: int = 0):
+        """A batch in mtb_classify_batch's flat layout (uint8 bases, n + 1 uint64 offsets), or device
+        pointers (ints) with flags = MTB_INPUT_DEVICE and off1 = (pointer, n_reads)."""
+        if isinstance(off1, tuple):
+            p_off1, n = off1
+            p_seq1, p_seq2, p_off2 = seq1, seq2, (off2[0] if off2 else None)
+        else:
+            seq1 = np.ascontiguousarray(seq1, np.uint8)
+            off1 = np.ascontiguousarray(off1, np.uint64)
+            n = len(off1) - 1
+            p_seq1, p_off1, p_seq2, p_off2 = seq1.ctypes.data, off1.ctypes.data, None, None
+            if seq2 is not None:
+                seq2 = np.ascontiguousarray(seq2, np.uint8)
+                off2 = np.ascontiguousarray(off2, np.uint64)
+                p_seq2, p_off2 = seq2.ctypes.data, off2.ctypes.data
+        check(lib().mtb_group_add_batch(self._h, p_seq1, p_off1, p_seq2, p_off2, n, flags), "mtb_group_add_batch")
+        self.reads += n
+
+    def add_reads(self, reads1, reads2=None):
+        """A batch from lists of str / bytes reads."""
+        s1, o1 = _flat(reads1)
+        if reads2 is None:
+            return self.add_batch(s1, o1)
+        s2, o2 = _flat(reads2)
+        return self.add_batch(s1, o1, s2, o2)
+
+    def kmers(self):
+        """(values, read_ids) of the k-mer instances extracted so far."""
+        n = ctypes.c_uint64()
+        check(lib().mtb_group_get_kmers(self._h, None, None, 0, ctypes.byref(n)), "mtb_group_get_kmers")
+        v, r = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint32)
+        check(lib().mtb_group_get_kmers(self._h, v.ctypes.data, r.ctypes.data, n.value, ctypes.byref(n)),
+              "mtb_group_get_kmers")
+        return v, r
+
+    def build_edges(self, pair_budget: int = 0) -> dict:
+        st = MtbGroupStats()
+        check(lib().mtb_group_build_edges(self._h, pair_budget, ctypes.byref(st)), "mtb_group_build_edges")
+        self.stats = stats_dict(st)
+        return self.stats
+
+    def edges(self) -> np.ndarray:
+        n = ctypes.c_uint64()
+        check(lib().mtb_group_get_edges(self._h, None, 0, ctypes.byref(n)), "mtb_group_get_edges")
+        e = np.zeros(n.value, RELATION_DTYPE)
+        check(lib().mtb_group_get_edges(self._h, e.ctypes.data, n.value, ctypes.byref(n)), "mtb_group_get_edges")
+        return e
+
+    def skipped(self):
+        """(values, m) of the k-mers over the cap."""
+        n = ctypes.c_uint64()
+        check(lib().mtb_group_get_skipped(self._h, None, None, 0, ctypes.byref(n)), "mtb_group_get_skipped")
+        v, m = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint32)
+        check(lib().mtb_group_get_skipped(self._h, v.ctypes.data, m.ctypes.data, n.value, ctypes.byref(n)),
+              "mtb_group_get_skipped")
+        return v, m
+
+    def finish(self):
+        """The three phases on the resident edges: (groupMap of reads + 1 entries, stats)."""
+        gm = np.zeros(self.reads + 1, np.uint32)
+        st = MtbGroupStats()
+        check(lib().mtb_group_finish(self._h, gm.ctypes.data, ctypes.byref(st)), "mtb_group_finish")
+        self.stats = stats_dict(st)
+        return gm, self.stats
+
+
+def group_reads(query1, query2, out_dir, par: GroupParams = None, device: int = 0, pair_budget: int = 0,
+                max_reads: int = 1 << 20, max_bases: int = 1 << 30):
+    """groupGeneration over FASTA / FASTQ files (plain or gzip): batches streamed through mtb_reader_*,
+    the graph and the phases on the device; writes out_dir/groupMap, groups and skipped_kmers
+    ("value \\t m" per skipped k-mer). Returns (groupMap, stats)."""
+    import pathlib
+
+    from ._abi import MtbReadBatch
+
+    par = par or GroupParams()
+    if (par.seq_mode == 2) != bool(query2):
+        raise ValueError("seq_mode 2 takes two query files, seq_mode 1 and 3 take one")
+    L = lib()
+    rd = ctypes.c_void_p()
+    check(L.mtb_reader_open(str(query1).encode(), str(query2).encode() if query2 else None, ctypes.byref(rd)),
+          "mtb_reader_open")
+    try:
+        with ReadGrouper(par, device) as g:
+            batch = MtbReadBatch()
+            while True:
+                check(L.mtb_reader_next(rd, max_reads, max_bases, ctypes.byref(batch)), "mtb_reader_next")
+                if batch.n_reads == 0:
+                    break
+                check(L.mtb_group_add_batch(g._h, batch.seq1, ctypes.cast(batch.off1, ctypes.c_void_p), batch.seq2,
+                                            ctypes.cast(batch.off2, ctypes.c_void_p) if query2 else None,
+                                            batch.n_reads, 0), "mtb_group_add_batch")
+                g.reads += batch.n_reads
+            g.build_edges(pair_budget)
+            sv, sm = g.skipped()
+            gm, st = g.finish()
+    finally:
+        L.mtb_reader_close(rd)
+    write_group_files(out_dir, gm)
+    with open(pathlib.Path(out_dir) / "skipped_kmers", "wb") as f:
+        f.write("".join(f"{v}\t{m}\n" for v, m in zip(sv.tolist(), sm.tolist())).encode())
+    return gm, st
