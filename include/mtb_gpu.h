@@ -598,9 +598,10 @@ typedef struct mtb_group_stats {
 void mtb_group_default_params(mtb_group_params* par);
 
 /* A grouping run on one device: batches of reads in, the shared-k-mer graph and the groupMap out.
- * Everything stays resident in HBM (no kmer_delta_* / subGraph_* spill). Out of scope: the common-k-mer
- * filter (the graph is over all extracted k-mers, and total k-mers is their count), masking,
- * mergeGraph_one, GroupApplier, more than one GPU. */
+ * Everything stays resident in HBM (no kmer_delta_* / subGraph_* spill). With a common-k-mer set
+ * attached (below) every batch goes through filterCommonKmers before it is stored; without one the
+ * graph is over all extracted k-mers. Out of scope: masking, mergeGraph_one, GroupApplier, more than
+ * one GPU. */
 typedef struct mtb_grouper mtb_grouper;
 int mtb_group_open(const mtb_group_params* par, int device, mtb_grouper** out);
 void mtb_group_close(mtb_grouper* g);
@@ -622,16 +623,58 @@ int mtb_group_get_kmers(mtb_grouper* g, uint64_t* values, uint32_t* read_ids, ui
  * rounds of at most pair_budget (0: from free HBM), one thread per pair; a budget below the largest
  * kept clique is MTB_ERR_ARG; MTB_ERR_OOM (the bytes needed in mtb_last_error) when the graph does
  * not fit the device. May be called again (another budget); no batch may follow it.
- * stats->ms: [0] extraction (all batches), [1] k-mer sort, [2] run pass, [3] pair rounds (emit, sort,
+ * stats->ms: [0] extraction (all batches; with a common-k-mer set it spans the filter too, whose own
+ * stages are in mtb_group_filter_stats.ms), [1] k-mer sort, [2] run pass, [3] pair rounds (emit, sort,
  * reduce), [4] cross-round merge and records. */
 int mtb_group_build_edges(mtb_grouper* g, uint64_t pair_budget, mtb_group_stats* stats);
 /* The edges, (id1, id2) ascending; MTB_RETRY (n set) when cap is too small. */
 int mtb_group_get_edges(mtb_grouper* g, mtb_relation* out, uint64_t cap, uint64_t* n);
 /* The skipped k-mers (value, m), value ascending (the reference logs them as "value \t m"). */
 int mtb_group_get_skipped(mtb_grouper* g, uint64_t* values, uint32_t* m, uint64_t cap, uint64_t* n);
-/* The three phases on the resident edges, total k-mers = the instances extracted; group_map: reads + 1
- * entries (entry 0 unused). Reads without a k-mer get label 0. */
+/* The three phases on the resident edges, total k-mers = the instances stored (with a common-k-mer
+ * set: the kept ones, the reference's totalFilteredKmers; mtb_group_stats.kmers is that count);
+ * group_map: reads + 1 entries (entry 0 unused). Reads without a k-mer get label 0. With every k-mer
+ * filtered away the core threshold resolves below 2: MTB_ERR_ARG, as the reference exits. */
 int mtb_group_finish(mtb_grouper* g, uint32_t* group_map, mtb_group_stats* stats);
+
+/* ---- the common-k-mer filter (GroupGenerator::filterCommonKmers, GroupGenerator.cpp:228-408) ------
+ * An extracted instance (value, read, pos) is hit iff its value is in the common-k-mer DB; an instance
+ * is removed iff a hit instance of the same read lies within one nucleotide of it (|pos - pos_hit| <= 1,
+ * COMMON_KMER_NEIGHBOR_SPAN; frames and strands do not enter); the others are kept and stored. pos is
+ * the scanners' nucleotide position (mate 2 after getMaxCoveredLength(len1) + 3).
+ * The set is attached before the first batch, at most once (MTB_ERR_ARG otherwise); its distinct values
+ * stay in HBM under a two-level sampled index (see mtb_group_filter_constants). MTB_ERR_OOM (the bytes
+ * needed in mtb_last_error) when it does not fit. With a set attached each stored instance also keeps
+ * its 4-B pos until mtb_group_build_edges. */
+/* db_dir/diffIdx decoded on the device (values must not descend, the file must end on a k-mer:
+ * MTB_ERR_DB); split and info are not read. db_dir/kmer_params ("key int" pairs), when present, must
+ * name the run's syncmer and smer_len and kmer_format 3 (syncmer 0) or 5 (syncmer 1): MTB_ERR_ARG with
+ * both sides' values otherwise, as groupGeneration.cpp:101-130; absent, params_checked stays 0. */
+int mtb_group_set_common_db(mtb_grouper* g, const char* db_dir);
+/* The same set from a host array, ascending, repeats allowed (MTB_ERR_ARG when it descends); n = 0 is
+ * an empty set: the filter runs and removes nothing. */
+int mtb_group_set_common_kmers(mtb_grouper* g, const uint64_t* values, uint64_t n);
+/* Over a run removed + kept = extracted and hit <= removed. ms, summed over the batches: [0] set load,
+ * [1] membership, [2] neighbourhood, [3] compaction. */
+typedef struct mtb_group_filter_stats {
+    uint64_t extracted, db_values, hit, removed, kept;
+    int32_t params_checked, reserved;
+    float ms[4];
+} mtb_group_filter_stats;
+int mtb_group_get_filter_stats(mtb_grouper* g, mtb_group_filter_stats* out);
+/* Staged: pos of the instances mtb_group_get_kmers returns, in the same order; only with a set attached
+ * and before mtb_group_build_edges (MTB_ERR_ARG otherwise). MTB_RETRY (n set) when cap is too small. */
+int mtb_group_get_kmer_pos(mtb_grouper* g, uint32_t* pos, uint64_t cap, uint64_t* n);
+/* The filter's membership and neighbourhood kernels alone on host arrays: n instances in read order
+ * (read_ids non-descending, pos < 2^31 in any order within a read) against n_db ascending values;
+ * hit[i], keep[i] = 0 / 1. MTB_ERR_ARG: read_ids descend, db_values descend, a pos >= 2^31. */
+int mtb_group_filter_common(int device, const uint64_t* db_values, uint64_t n_db, const uint64_t* values,
+                            const uint32_t* read_ids, const uint32_t* pos, uint64_t n, uint8_t* hit, uint8_t* keep);
+/* The sizes at which the filter's kernels change path: out[0] values per leaf of the set (the last
+ * search runs inside one leaf), out[1] entries of the top level held in LDS (a set of more than
+ * out[0] * out[1] values samples its leaf heads), out[2] bits of a read's on-chip position bitmap (a
+ * read whose last hit lies at pos >= out[2] - 1 keeps its bitmap in HBM), out[3] 0. */
+void mtb_group_filter_constants(uint32_t out[4]);
 
 /* The three phases alone on host edges over reads 1 .. n_reads (makeGroups, mergeBySupport at its
  * defaults, makeGroupsPhase2: GroupGenerator.cpp:1469-2053). Thresholds as GroupGenerator.cpp:171-192

@@ -128,7 +128,7 @@ class MtbEmStats(ctypes.Structure):
                 ("delta", ctypes.c_double)]
 
 
-# read grouping (include/mtb_gpu.h: mtb_group_params, mtb_relation, mtb_group_stats)
+# read grouping (include/mtb_gpu.h: mtb_group_params, mtb_relation, mtb_group_stats, mtb_group_filter_stats)
 class MtbGroupParams(ctypes.Structure):
     _fields_ = [("seq_mode", ctypes.c_int32), ("syncmer", ctypes.c_int32), ("smer_len", ctypes.c_int32),
                 ("max_kmer_reads", ctypes.c_int32), ("max_kmer_quantile", ctypes.c_float),
@@ -144,6 +144,12 @@ class MtbGroupStats(ctypes.Structure):
                 ("hist_kmers", ctypes.c_uint64 * 64), ("hist_pairs", ctypes.c_uint64 * 64),
                 ("groups_after", ctypes.c_uint64 * 3), ("grouped_after", ctypes.c_uint64 * 3),
                 ("core_thr", ctypes.c_int32), ("weak_thr", ctypes.c_int32), ("ms", ctypes.c_float * 8)]
+
+
+class MtbGroupFilterStats(ctypes.Structure):
+    _fields_ = [("extracted", ctypes.c_uint64), ("db_values", ctypes.c_uint64), ("hit", ctypes.c_uint64),
+                ("removed", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("params_checked", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("ms", ctypes.c_float * 4)]
 
 
 RELATION_DTYPE = np.dtype([("id1", "<u4"), ("id2", "<u4"), ("weight", "<u2"), ("pad", "<u2")])

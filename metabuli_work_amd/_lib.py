@@ -7,8 +7,8 @@ entry point raises. Build it with `python -c "import __graft_entry__ as g; g.bui
 import ctypes
 import pathlib
 
-from ._abi import (MtbClassifyOpts, MtbClassifyStats, MtbDbHost, MtbDbResident, MtbEmStats, MtbGroupParams, MtbGroupStats,
-                   MtbParams, MtbReadBatch)
+from ._abi import (MtbClassifyOpts, MtbClassifyStats, MtbDbHost, MtbDbResident, MtbEmStats, MtbGroupFilterStats,
+                   MtbGroupParams, MtbGroupStats, MtbParams, MtbReadBatch)
 
 _HERE = pathlib.Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libmtbgpu.so"
@@ -29,6 +29,8 @@ EXPORTED = [
     "mtb_merge_db", "mtb_merge_db_dirs", "mtb_merge_last_ms", "mtb_merge_tile_items", "mtb_scan_u32",
     "mtb_group_default_params", "mtb_group_make_groups", "mtb_group_open", "mtb_group_close", "mtb_group_add_batch",
     "mtb_group_get_kmers", "mtb_group_build_edges", "mtb_group_get_edges", "mtb_group_get_skipped", "mtb_group_finish",
+    "mtb_group_set_common_db", "mtb_group_set_common_kmers", "mtb_group_get_filter_stats", "mtb_group_get_kmer_pos",
+    "mtb_group_filter_common", "mtb_group_filter_constants",
 ]
 
 
@@ -122,6 +124,13 @@ def lib() -> ctypes.CDLL:
     L.mtb_group_get_edges.argtypes = [vp, vp, u64, P(u64)]
     L.mtb_group_get_skipped.argtypes = [vp, vp, vp, u64, P(u64)]
     L.mtb_group_finish.argtypes = [vp, vp, P(MtbGroupStats)]
+    L.mtb_group_set_common_db.argtypes = [vp, ctypes.c_char_p]
+    L.mtb_group_set_common_kmers.argtypes = [vp, vp, u64]
+    L.mtb_group_get_filter_stats.argtypes = [vp, P(MtbGroupFilterStats)]
+    L.mtb_group_get_kmer_pos.argtypes = [vp, vp, u64, P(u64)]
+    L.mtb_group_filter_common.argtypes = [i32, vp, u64, vp, vp, vp, u64, vp, vp]
+    L.mtb_group_filter_constants.argtypes = [P(u32 * 4)]
+    L.mtb_group_filter_constants.restype = None
     L.mtb_debug_tables.argtypes = [vp, vp, vp]
     L.mtb_debug_tables.restype = None
     _LIB = L

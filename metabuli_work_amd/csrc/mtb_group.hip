@@ -1,6 +1,7 @@
 // Read grouping on the GPU (the reference fork's src/read-group/, workflow groupGeneration). First half:
 // the three grouping phases over a resident edge list; second half: the shared-k-mer graph those edges
-// come from (AA 12-mer extraction, sort, run pass, pair rounds) and the mtb_group_* entry points.
+// come from (AA 12-mer extraction, the common-k-mer filter, sort, run pass, pair rounds) and the
+// mtb_group_* entry points.
 //   Phase 1   makeGroups        (GroupGenerator.cpp:1469-1552): union id1, id2 of every edge with
 //             weight > coreThr; a read is grouped iff such an edge touches it; label = smallest read ID
 //   Phase 1.5 mergeBySupport    (GroupGenerator.cpp:1577-1976, mergeSupportRatio = 0, mergeMaxUnitReads = 0):
@@ -372,7 +373,8 @@ __global__ void __launch_bounds__(256) k_extract_aa12(const uint8_t* __restrict_
                                                       const ReadMeta* __restrict__ meta, const uint64_t* __restrict__ uOff,
                                                       const uint32_t* __restrict__ unitRead, uint64_t nUnits, int paired,
                                                       GroupTables tabs, int syncmer, int smerLen, uint32_t idBase,
-                                                      uint64_t* __restrict__ keys, uint32_t* __restrict__ ids) {
+                                                      uint64_t* __restrict__ keys, uint32_t* __restrict__ ids,
+                                                      uint32_t* __restrict__ pos) {
     __shared__ uint8_t sBase[256];
     __shared__ int8_t sAA[64];
     sBase[threadIdx.x] = tabs.base[threadIdx.x];
@@ -408,6 +410,11 @@ __global__ void __launch_bounds__(256) k_extract_aa12(const uint8_t* __restrict_
     uint64_t* kOut = keys + u * kGroupChunk;
     uint32_t* iOut = ids + u * kGroupChunk;
     const uint32_t id = idBase + r + 1;
+    // pos (null without a common-k-mer set): the scanners' nucleotide position of window P of the frame —
+    // frame + 3 P forward, seqEnd - 3 (P + 12) + 1 on a reverse frame (KmerScanner.h:253-257,
+    // SyncmerScanner.h:287-289), mate 2 after getMaxCoveredLength(len1) + 3 (KmerExtractor.cpp:341-345)
+    uint32_t* pOut = pos ? pos + u * kGroupChunk : nullptr;
+    const int posBase = (fwd ? s0 : e0 - 3 * kGroupK + 1) + (mate ? max_covered_length(m.len1) + 3 : 0);
     for (int j = pFirst; j < pFirst + nWin + kGroupK - 1; j++) {
         const int d = fwd ? 1 : -1;
         const int c0 = fwd ? s0 + 3 * j : e0 - 3 * j;
@@ -435,8 +442,13 @@ __global__ void __launch_bounds__(256) k_extract_aa12(const uint8_t* __restrict_
         }
         kOut[p] = emit ? (aaAcc & kAA12Mask) : kSentinel;
         iOut[p] = id;
+        if (pOut) pOut[p] = (uint32_t)(fwd ? posBase + 3 * (pFirst + p) : posBase - 3 * (pFirst + p));
     }
-    for (int p = max(nWin, 0); p < (int)kGroupChunk; p++) { kOut[p] = kSentinel; iOut[p] = id; }
+    for (int p = max(nWin, 0); p < (int)kGroupChunk; p++) {
+        kOut[p] = kSentinel;
+        iOut[p] = id;
+        if (pOut) pOut[p] = 0;
+    }
 }
 
 __global__ void k_flag_kept(const uint64_t* __restrict__ keys, uint64_t n, uint32_t* __restrict__ flag) {
@@ -448,6 +460,181 @@ __global__ void k_compact_kmers(const uint64_t* __restrict__ keys, const uint32_
                                 uint32_t* __restrict__ dIds) {
     MTB_GRID_STRIDE(i, n)
         if (keys[i] != kSentinel) { dKeys[off[i]] = keys[i]; dIds[off[i]] = ids[i]; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The common-k-mer filter (filterCommonKmers, GroupGenerator.cpp:228-408): an instance is hit iff its
+// value is in the set, removed iff a hit of its read lies within one nucleotide of it.
+// The set: its distinct values ascending in HBM, cut into leaves of kSetLeaf values; mid holds every
+// leaf's first value; top holds every T-th mid entry, at most kSetTop of them (T = 1 up to
+// kSetLeaf * kSetTop values: top = mid). A block stages top in LDS once and answers its queries by
+// three searches: top in LDS, at most T mid entries (one stretch of HBM, shared through L2 by every
+// query between the same two top entries), one leaf (512 B).
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t kSetLeaf = 64;
+constexpr uint32_t kSetTop = 4096;
+constexpr uint32_t kNbrLdsBits = 4096;  // a read's position bitmap held on chip
+
+struct SetIndex {
+    const uint64_t *set, *mid, *top;
+    uint64_t n, nMid, T;
+    uint32_t nTop;
+};
+
+// flag the first of each run of equal values (prev: the value before vals[0], when hasPrev); a value
+// below the one before it sets *desc
+__global__ void k_set_flag(const uint64_t* __restrict__ vals, uint64_t n, int hasPrev, uint64_t prev,
+                           uint32_t* __restrict__ flag, int* __restrict__ desc) {
+    MTB_GRID_STRIDE(i, n) {
+        const uint64_t v = vals[i];
+        const bool first = i == 0 && !hasPrev;
+        const uint64_t b = i ? vals[i - 1] : prev;
+        if (!first && v < b) *desc = 1;
+        flag[i] = first || v != b;
+    }
+}
+__global__ void k_compact_u64(const uint64_t* __restrict__ in, const uint32_t* __restrict__ flag,
+                              const uint64_t* __restrict__ off, uint64_t n, uint64_t* __restrict__ out) {
+    MTB_GRID_STRIDE(i, n)
+        if (flag[i]) out[off[i]] = in[i];
+}
+__global__ void k_compact_u32(const uint32_t* __restrict__ in, const uint32_t* __restrict__ flag,
+                              const uint64_t* __restrict__ off, uint64_t n, uint32_t* __restrict__ out) {
+    MTB_GRID_STRIDE(i, n)
+        if (flag[i]) out[off[i]] = in[i];
+}
+__global__ void k_set_sample(const uint64_t* __restrict__ src, uint64_t stride, uint64_t nOut, uint64_t* __restrict__ out) {
+    MTB_GRID_STRIDE(i, nOut) out[i] = src[i * stride];
+}
+
+// hit[i] = keys[i] is in the set (a sentinel slot never is)
+__global__ void __launch_bounds__(256) k_set_member(SetIndex ix, const uint64_t* __restrict__ keys, uint64_t n,
+                                                    int skipSentinel, uint8_t* __restrict__ hit) {
+    __shared__ uint64_t sTop[kSetTop];
+    for (uint32_t i = threadIdx.x; i < ix.nTop; i += blockDim.x) sTop[i] = ix.top[i];
+    __syncthreads();
+    MTB_GRID_STRIDE(i, n) {
+        const uint64_t q = keys[i];
+        uint8_t h = 0;
+        if (!(skipSentinel && q == kSentinel) && q >= sTop[0]) {
+            uint32_t lo = 0, hi = ix.nTop - 1;  // the last top entry <= q
+            while (lo < hi) {
+                const uint32_t m = (lo + hi + 1) >> 1;
+                if (sTop[m] <= q) lo = m; else hi = m - 1;
+            }
+            uint64_t a = (uint64_t)lo * ix.T, b = a + ix.T < ix.nMid ? a + ix.T - 1 : ix.nMid - 1;  // the last leaf head <= q
+            while (a < b) {
+                const uint64_t m = a + (b - a + 1) / 2;
+                if (ix.mid[m] <= q) a = m; else b = m - 1;
+            }
+            uint64_t l = a * kSetLeaf, r = l + kSetLeaf < ix.n ? l + kSetLeaf : ix.n;
+            const uint64_t end = r;
+            while (l < r) {
+                const uint64_t m = l + ((r - l) >> 1);
+                if (ix.set[m] < q) l = m + 1; else r = m;
+            }
+            h = l < end && ix.set[l] == q;
+        }
+        hit[i] = h;
+    }
+}
+
+// flag the first instance of each read (read IDs non-descending; a descent sets *desc)
+__global__ void k_flag_read_heads(const uint32_t* __restrict__ ids, uint64_t n, uint32_t* __restrict__ flag,
+                                  int* __restrict__ desc) {
+    MTB_GRID_STRIDE(i, n) {
+        if (i && ids[i] < ids[i - 1]) *desc = 1;
+        flag[i] = i == 0 || ids[i] != ids[i - 1];
+    }
+}
+__global__ void k_pos_range(const uint32_t* __restrict__ pos, uint64_t n, int* __restrict__ bad) {
+    MTB_GRID_STRIDE(i, n) if (pos[i] >> 31) *bad = 1;
+}
+
+// Segment g (a read) holds the instances [off[g] * mul, off[g + 1] * mul). One wave per segment: the
+// words of the bitmap its hits need (bits 0 .. last hit + 1), 0 when the on-chip bitmap holds them.
+__global__ void __launch_bounds__(64) k_seg_span(const uint64_t* __restrict__ off, uint32_t mul, uint64_t nSeg,
+                                                 const uint32_t* __restrict__ pos, const uint8_t* __restrict__ hit,
+                                                 uint32_t* __restrict__ bigWords) {
+    for (uint64_t g = blockIdx.x; g < nSeg; g += gridDim.x) {
+        const uint64_t a = off[g] * mul, b = off[g + 1] * mul;
+        uint32_t mx = 0;
+        for (uint64_t i = a + threadIdx.x; i < b; i += 64)
+            if (hit[i]) mx = pos[i] > mx ? pos[i] : mx;
+#pragma unroll
+        for (int d = 32; d; d >>= 1) {
+            const uint32_t o = __shfl_xor(mx, d, 64);
+            mx = o > mx ? o : mx;
+        }
+        if (threadIdx.x == 0) {
+            const uint64_t span = (uint64_t)mx + 2;
+            bigWords[g] = span > kNbrLdsBits ? (uint32_t)((span + 31) / 32) : 0u;
+        }
+    }
+}
+
+// removed[i] = a hit of i's segment lies at pos[i] - 1, pos[i] or pos[i] + 1. A block per segment: hits
+// set their bit in the segment's own bitmap, then every instance tests its three bits; bits outside the
+// bitmap (below 0, past the last hit + 1) are clear, so neither end reaches another read. big = 0: the
+// segments whose bitmap fits LDS; big = 1: the others, bitmaps in HBM (bigBits, zeroed, at bigOff words).
+__global__ void __launch_bounds__(256) k_neighbours(const uint64_t* __restrict__ off, uint32_t mul, uint64_t nSeg,
+                                                    const uint32_t* __restrict__ pos, const uint8_t* __restrict__ hit,
+                                                    const uint32_t* __restrict__ bigWords,
+                                                    const uint64_t* __restrict__ bigOff, uint32_t* bigBits, int big,
+                                                    uint8_t* __restrict__ removed) {
+    __shared__ uint32_t sBits[kNbrLdsBits / 32];
+    for (uint64_t g = blockIdx.x; g < nSeg; g += gridDim.x) {
+        const uint32_t bw = bigWords[g];
+        if ((bw != 0) != (big != 0)) continue;  // uniform over the block
+        const uint64_t a = off[g] * mul, b = off[g + 1] * mul;
+        uint32_t* bits = big ? bigBits + bigOff[g] : sBits;
+        const uint64_t nBits = big ? (uint64_t)bw * 32 : kNbrLdsBits;
+        if (!big) {
+            for (uint32_t w = threadIdx.x; w < kNbrLdsBits / 32; w += blockDim.x) sBits[w] = 0;
+            __syncthreads();
+        }
+        for (uint64_t i = a + threadIdx.x; i < b; i += blockDim.x)
+            if (hit[i]) atomicOr(bits + (pos[i] >> 5), 1u << (pos[i] & 31u));
+        __syncthreads();
+        for (uint64_t i = a + threadIdx.x; i < b; i += blockDim.x) {
+            const uint64_t p = pos[i];
+            bool r = false;
+#pragma unroll
+            for (int d = -1; d <= 1; d++) {
+                const uint64_t x = p + (uint64_t)(int64_t)d;  // p = 0, d = -1 wraps past nBits: clear
+                if (x < nBits) {
+                    const uint32_t w = big ? __hip_atomic_load(bits + (x >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                           : bits[x >> 5];
+                    r = r || ((w >> (x & 31u)) & 1u);
+                }
+            }
+            removed[i] = r;
+        }
+        __syncthreads();  // the next segment clears the bitmap
+    }
+}
+
+// out[0] non-sentinel slots, out[1] hits, out[2] removed non-sentinel slots (keys null: no sentinels)
+__global__ void __launch_bounds__(256) k_filter_counts(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ hit,
+                                                       const uint8_t* __restrict__ removed, uint64_t n,
+                                                       unsigned long long* __restrict__ out) {
+    unsigned long long c[3] = {0, 0, 0};
+    MTB_GRID_STRIDE(i, n) {
+        const bool real = !keys || keys[i] != kSentinel;
+        c[0] += real;
+        c[1] += real && hit[i];
+        c[2] += real && removed[i];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+#pragma unroll
+        for (int d = 32; d; d >>= 1) c[k] += __shfl_xor(c[k], d, 64);
+        if ((threadIdx.x & 63) == 0 && c[k]) atomicAdd(out + k, c[k]);
+    }
+}
+__global__ void k_flag_unfiltered(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ removed, uint64_t n,
+                                  uint32_t* __restrict__ flag) {
+    MTB_GRID_STRIDE(i, n) flag[i] = keys[i] != kSentinel && !removed[i];
 }
 
 // the sorted instances: flag the first of each (value, read)
@@ -674,12 +861,175 @@ struct mtb_grouper {
     std::vector<uint64_t> skipValues;
     std::vector<uint32_t> skipM;
     mtb_group_stats stats;
-    mtb_grouper() : tables(make_tables()) { memset(&stats, 0, sizeof(stats)); }
+    // the common-k-mer set (hasSet) and the kept instances' positions, held until the edges are built
+    bool hasSet = false, started = false;
+    DVec setVals{8}, pos{4};
+    Buf setMid, setTop;
+    SetIndex setIx{};
+    mtb_group_filter_stats fst;
+    mtb_grouper() : tables(make_tables()) {
+        memset(&stats, 0, sizeof(stats));
+        memset(&fst, 0, sizeof(fst));
+    }
     const uint64_t* sortedKeys() const { return keys.as<uint64_t>(); }
     const uint32_t* sortedIds() const { return ids.as<uint32_t>(); }
 };
 
 namespace {
+
+struct EvPair {  // two events around a stage, destroyed on every return path
+    hipEvent_t a = nullptr, b = nullptr;
+    hipError_t create() {
+        hipError_t e = hipEventCreate(&a);
+        return e == hipSuccess ? hipEventCreate(&b) : e;
+    }
+    ~EvPair() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+};
+
+#define GRP_SET_OOM(e_, bytes_)                                                                                 \
+    do {                                                                                                        \
+        (void)hipGetLastError();                                                                                \
+        set_error("the common k-mer set does not fit the device: " + std::to_string(bytes_) + " bytes needed"); \
+        return (e_) == hipErrorOutOfMemory ? MTB_ERR_OOM : MTB_ERR_HIP;                                         \
+    } while (0)
+
+// The distinct values of n ascending device values (prev: the value before them, when hasPrev) appended
+// to set at nSet. flag: n u32, off: n + 1 u64, tmp: scan_tmp_elems(n) u64, dDesc: a zeroed device word.
+int append_distinct(DVec& set, uint64_t& nSet, const uint64_t* vals, uint64_t n, bool hasPrev, uint64_t prev,
+                    uint32_t* flag, uint64_t* off, void* tmp, int* dDesc, bool* descending) {
+    if (!n) return MTB_OK;
+    k_set_flag<<<stride_grid(n), 256>>>(vals, n, hasPrev, prev, flag, dDesc);
+    exclusive_scan_u32(flag, n, off, tmp, nullptr);
+    uint64_t add = 0;
+    int desc = 0;
+    GRP_TRY(hipMemcpy(&add, off + n, 8, hipMemcpyDeviceToHost));
+    GRP_TRY(hipMemcpy(&desc, dDesc, 4, hipMemcpyDeviceToHost));
+    if (desc) { *descending = true; return MTB_OK; }
+    const hipError_t e = set.reserve(nSet + add, nSet);
+    if (e != hipSuccess) GRP_SET_OOM(e, (nSet + add) * 8);
+    k_compact_u64<<<stride_grid(n), 256>>>(vals, flag, off, n, set.as<uint64_t>() + nSet);
+    GRP_TRY(hipGetLastError());
+    nSet += add;
+    return MTB_OK;
+}
+
+// the two sampled levels over nSet distinct values
+int build_set_index(SetIndex& ix, const uint64_t* set, uint64_t nSet, Buf& mid, Buf& top) {
+    ix = SetIndex{};
+    ix.set = set;
+    ix.n = nSet;
+    if (!nSet) return MTB_OK;
+    ix.nMid = (nSet + kSetLeaf - 1) / kSetLeaf;
+    ix.T = (ix.nMid + kSetTop - 1) / kSetTop;
+    ix.nTop = (uint32_t)((ix.nMid + ix.T - 1) / ix.T);
+    hipError_t e = mid.alloc(8 * ix.nMid);
+    if (e == hipSuccess) e = top.alloc(8 * (uint64_t)ix.nTop);
+    if (e != hipSuccess) GRP_SET_OOM(e, 8 * (ix.nMid + ix.nTop));
+    k_set_sample<<<stride_grid(ix.nMid), 256>>>(set, kSetLeaf, ix.nMid, mid.as<uint64_t>());
+    k_set_sample<<<stride_grid(ix.nTop), 256>>>(mid.as<uint64_t>(), ix.T, ix.nTop, top.as<uint64_t>());
+    GRP_TRY(hipGetLastError());
+    ix.mid = mid.as<uint64_t>();
+    ix.top = top.as<uint64_t>();
+    return MTB_OK;
+}
+
+// hit and removed (n bytes each) of n instances in nSeg segments (segment g: [off[g] * mul, off[g + 1] * mul));
+// ms (nullable): [0] += membership, [1] += neighbourhood
+int run_filter(const SetIndex& ix, const uint64_t* keys, int skipSentinel, const uint32_t* pos, const uint64_t* off,
+               uint32_t mul, uint64_t nSeg, uint64_t n, uint8_t* hit, uint8_t* removed, float* ms) {
+    if (!n) return MTB_OK;
+    EvPair m, nb;
+    GRP_TRY(m.create());
+    GRP_TRY(nb.create());
+    GRP_TRY(hipEventRecord(m.a, nullptr));
+    if (ix.n) k_set_member<<<std::min(stride_grid(n), 2048u), 256>>>(ix, keys, n, skipSentinel, hit);
+    else GRP_TRY(hipMemsetAsync(hit, 0, n, nullptr));
+    GRP_TRY(hipEventRecord(m.b, nullptr));
+    GRP_TRY(hipEventRecord(nb.a, nullptr));
+    Buf bigWords, bigOff, tmp, bigBits;
+    if (ix.n && nSeg) {
+        GRP_TRY(bigWords.alloc(4 * nSeg));
+        GRP_TRY(bigOff.alloc(8 * (nSeg + 1)));
+        GRP_TRY(tmp.alloc(8 * scan_tmp_elems(nSeg)));
+        const unsigned grid = (unsigned)std::min<uint64_t>(nSeg, 1u << 20);
+        k_seg_span<<<grid, 64>>>(off, mul, nSeg, pos, hit, bigWords.as<uint32_t>());
+        exclusive_scan_u32(bigWords.as<uint32_t>(), nSeg, bigOff.as<uint64_t>(), tmp.p, nullptr);
+        uint64_t words = 0;
+        GRP_TRY(hipMemcpy(&words, bigOff.as<uint64_t>() + nSeg, 8, hipMemcpyDeviceToHost));
+        k_neighbours<<<grid, 64>>>(off, mul, nSeg, pos, hit, bigWords.as<uint32_t>(), bigOff.as<uint64_t>(), nullptr, 0,
+                                   removed);
+        if (words) {  // reads whose hits reach past the on-chip bitmap: theirs in HBM
+            const hipError_t e = bigBits.alloc(4 * words);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("the filter's position bitmaps do not fit the device: " + std::to_string(4 * words) + " bytes needed");
+                return e == hipErrorOutOfMemory ? MTB_ERR_OOM : MTB_ERR_HIP;
+            }
+            GRP_TRY(hipMemsetAsync(bigBits.p, 0, 4 * words, nullptr));
+            k_neighbours<<<(unsigned)std::min<uint64_t>(nSeg, 4096), 256>>>(off, mul, nSeg, pos, hit, bigWords.as<uint32_t>(),
+                                                                          bigOff.as<uint64_t>(), bigBits.as<uint32_t>(), 1,
+                                                                          removed);
+        }
+    } else {
+        GRP_TRY(hipMemsetAsync(removed, 0, n, nullptr));
+    }
+    GRP_TRY(hipGetLastError());
+    GRP_TRY(hipEventRecord(nb.b, nullptr));
+    GRP_TRY(hipDeviceSynchronize());
+    if (ms) {
+        float t = 0;
+        GRP_TRY(hipEventElapsedTime(&t, m.a, m.b));
+        ms[0] += t;
+        GRP_TRY(hipEventElapsedTime(&t, nb.a, nb.b));
+        ms[1] += t;
+    }
+    return MTB_OK;
+}
+
+int attachable(mtb_grouper* g) {
+    if (!g) { set_error("null argument"); return MTB_ERR_ARG; }
+    if (g->hasSet) { set_error("a common k-mer set is attached already"); return MTB_ERR_ARG; }
+    if (g->started) { set_error("the common k-mer set must be attached before the first batch"); return MTB_ERR_ARG; }
+    return MTB_OK;
+}
+
+// groupGeneration.cpp:101-130: all three keys compared, a key the file lacks reads as -1
+int check_kmer_params(mtb_grouper* g, const std::string& dir, int* checked) {
+    *checked = 0;
+    FILE* f = fopen((dir + "/kmer_params").c_str(), "r");
+    if (!f) return MTB_OK;
+    int dbSyncmer = -1, dbSmerLen = -1, dbKmerFormat = -1, value = 0;
+    char key[64];
+    while (fscanf(f, "%63s %d", key, &value) == 2) {
+        if (!strcmp(key, "syncmer")) dbSyncmer = value;
+        else if (!strcmp(key, "smer_len")) dbSmerLen = value;
+        else if (!strcmp(key, "kmer_format")) dbKmerFormat = value;
+    }
+    fclose(f);
+    const int syncmer = g->par.syncmer, smerLen = g->par.smer_len, kmerFormat = g->par.syncmer ? 5 : 3;
+    if (dbSyncmer != syncmer || dbSmerLen != smerLen || dbKmerFormat != kmerFormat) {
+        set_error("k-mer settings do not match the common k-mer DB at " + dir + ": DB syncmer " + std::to_string(dbSyncmer) +
+                  " smer_len " + std::to_string(dbSmerLen) + " kmer_format " + std::to_string(dbKmerFormat) +
+                  ", request syncmer " + std::to_string(syncmer) + " smer_len " + std::to_string(smerLen) +
+                  " kmer_format " + std::to_string(kmerFormat));
+        return MTB_ERR_ARG;
+    }
+    *checked = 1;
+    return MTB_OK;
+}
+
+// after the set's values are in g->setVals (n of them): index, flags, stats
+int finish_set(mtb_grouper* g, uint64_t nSet, const EvPair& ev) {
+    if (const int rc = build_set_index(g->setIx, g->setVals.as<uint64_t>(), nSet, g->setMid, g->setTop)) return rc;
+    GRP_TRY(hipEventRecord(ev.b, nullptr));
+    GRP_TRY(hipDeviceSynchronize());
+    float t = 0;
+    GRP_TRY(hipEventElapsedTime(&t, ev.a, ev.b));
+    g->fst.ms[0] += t;
+    g->fst.db_values = nSet;
+    g->hasSet = true;
+    return MTB_OK;
+}
 
 // sorted (key, count-or-nothing) items -> one (key, sum) per distinct key, appended to outK / outC at outN
 int reduce_sorted(const uint64_t* keys, const uint32_t* cnt, uint64_t n, DVec& outK, DVec& outC, uint64_t& outN,
@@ -938,6 +1288,7 @@ extern "C" int mtb_group_add_batch(mtb_grouper* g, const char* seq, const uint64
     if (g->built) { set_error("the edges are built: no more batches"); return MTB_ERR_ARG; }
     if (g->reads + n_reads >= 0xFFFFFFFFull) { set_error("2^32 - 1 reads or more"); return MTB_ERR_ARG; }
     if (!n_reads) return MTB_OK;
+    g->started = true;
     GRP_TRY(hipSetDevice(g->device));
     Buf hSeq1, hOff1, hSeq2, hOff2;
     const uint8_t* dSeq1 = (const uint8_t*)seq;
@@ -983,13 +1334,20 @@ extern "C" int mtb_group_add_batch(mtb_grouper* g, const char* seq, const uint64
     uint64_t kept = 0;
     if (nUnits) {
         const uint64_t slots = nUnits * kGroupChunk;
-        Buf sk, si, flag, off64, tmp2;
+        Buf sk, si, sp, hit, removed, counts, flag, off64, tmp2;
+        const bool filter = g->hasSet;
         GRP_TRY(unitRead.alloc(4 * nUnits));
         GRP_TRY(sk.alloc(8 * slots));
         GRP_TRY(si.alloc(4 * slots));
         GRP_TRY(flag.alloc(4 * slots));
         GRP_TRY(off64.alloc(8 * (slots + 1)));
         GRP_TRY(tmp2.alloc(8 * scan_tmp_elems(slots)));
+        if (filter) {
+            GRP_TRY(sp.alloc(4 * slots));
+            GRP_TRY(hit.alloc(slots));
+            GRP_TRY(removed.alloc(slots));
+            GRP_TRY(counts.alloc(8 * 3));
+        }
         launch_unit_read(uOff.as<uint64_t>(), n_reads, unitRead.as<uint32_t>(), nullptr);
         GroupTables tabs;
         for (int i = 0; i < 256; i++) tabs.base[i] = g->tables.base[i];
@@ -997,19 +1355,56 @@ extern "C" int mtb_group_add_batch(mtb_grouper* g, const char* seq, const uint64
         k_extract_aa12<<<(unsigned)((nUnits + 255) / 256), 256>>>(dSeq1, dOff1, dSeq2, dOff2, meta.as<ReadMeta>(),
                                                                   uOff.as<uint64_t>(), unitRead.as<uint32_t>(), nUnits, paired,
                                                                   tabs, g->par.syncmer != 0, g->par.syncmer ? g->par.smer_len : 5,
-                                                                  (uint32_t)g->reads, sk.as<uint64_t>(), si.as<uint32_t>());
-        k_flag_kept<<<stride_grid(slots), 256>>>(sk.as<uint64_t>(), slots, flag.as<uint32_t>());
+                                                                  (uint32_t)g->reads, sk.as<uint64_t>(), si.as<uint32_t>(),
+                                                                  filter ? sp.as<uint32_t>() : nullptr);
+        EvPair evC;
+        if (filter) {
+            // filterCommonKmers on the batch's slots (a read's slots are contiguous: its units), then the
+            // usual flag, scan and compact over what is left
+            GRP_TRY(evC.create());
+            if (const int rc = run_filter(g->setIx, sk.as<uint64_t>(), 1, sp.as<uint32_t>(), uOff.as<uint64_t>(), kGroupChunk,
+                                          n_reads, slots, hit.as<uint8_t>(), removed.as<uint8_t>(), g->fst.ms + 1))
+                return rc;
+            GRP_TRY(hipEventRecord(evC.a, nullptr));
+            GRP_TRY(hipMemsetAsync(counts.p, 0, 8 * 3, nullptr));
+            k_filter_counts<<<std::min(stride_grid(slots), 2048u), 256>>>(sk.as<uint64_t>(), hit.as<uint8_t>(),
+                                                                           removed.as<uint8_t>(), slots,
+                                                                           counts.as<unsigned long long>());
+            k_flag_unfiltered<<<stride_grid(slots), 256>>>(sk.as<uint64_t>(), removed.as<uint8_t>(), slots, flag.as<uint32_t>());
+        } else {
+            k_flag_kept<<<stride_grid(slots), 256>>>(sk.as<uint64_t>(), slots, flag.as<uint32_t>());
+        }
         exclusive_scan_u32(flag.as<uint32_t>(), slots, off64.as<uint64_t>(), tmp2.p, nullptr);
         GRP_TRY(hipMemcpy(&kept, off64.as<uint64_t>() + slots, 8, hipMemcpyDeviceToHost));
         hipError_t e = g->keys.reserve(g->kmers + kept, g->kmers);
         if (e == hipSuccess) e = g->ids.reserve(g->kmers + kept, g->kmers);
+        if (e == hipSuccess && filter) e = g->pos.reserve(g->kmers + kept, g->kmers);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            set_error("the k-mers do not fit the device: " + std::to_string((g->kmers + kept) * 12) + " bytes needed");
+            set_error("the k-mers do not fit the device: " + std::to_string((g->kmers + kept) * (filter ? 16 : 12)) + " bytes needed");
             return e == hipErrorOutOfMemory ? MTB_ERR_OOM : MTB_ERR_HIP;
         }
-        k_compact_kmers<<<stride_grid(slots), 256>>>(sk.as<uint64_t>(), si.as<uint32_t>(), slots, off64.as<uint64_t>(),
-                                                     g->keys.as<uint64_t>() + g->kmers, g->ids.as<uint32_t>() + g->kmers);
+        if (filter) {
+            k_compact_distinct<<<stride_grid(slots), 256>>>(sk.as<uint64_t>(), si.as<uint32_t>(), flag.as<uint32_t>(),
+                                                            off64.as<uint64_t>(), slots, g->keys.as<uint64_t>() + g->kmers,
+                                                            g->ids.as<uint32_t>() + g->kmers);
+            k_compact_u32<<<stride_grid(slots), 256>>>(sp.as<uint32_t>(), flag.as<uint32_t>(), off64.as<uint64_t>(), slots,
+                                                       g->pos.as<uint32_t>() + g->kmers);
+            GRP_TRY(hipEventRecord(evC.b, nullptr));
+            unsigned long long c[3];
+            GRP_TRY(hipMemcpy(c, counts.p, 8 * 3, hipMemcpyDeviceToHost));
+            float t = 0;
+            GRP_TRY(hipEventElapsedTime(&t, evC.a, evC.b));
+            g->fst.ms[3] += t;
+            if (c[0] - c[2] != kept) { set_error("the filter's counts disagree with its compaction"); return MTB_ERR_INTERNAL; }
+            g->fst.extracted += c[0];
+            g->fst.hit += c[1];
+            g->fst.removed += c[2];
+            g->fst.kept += kept;
+        } else {
+            k_compact_kmers<<<stride_grid(slots), 256>>>(sk.as<uint64_t>(), si.as<uint32_t>(), slots, off64.as<uint64_t>(),
+                                                         g->keys.as<uint64_t>() + g->kmers, g->ids.as<uint32_t>() + g->kmers);
+        }
         GRP_TRY(hipGetLastError());
     }
     GRP_TRY(hipEventRecord(e1, nullptr));
@@ -1038,6 +1433,7 @@ extern "C" int mtb_group_build_edges(mtb_grouper* g, uint64_t pair_budget, mtb_g
     if (!g) { set_error("null argument"); return MTB_ERR_ARG; }
     GRP_TRY(hipSetDevice(g->device));
     g->built = false;  // again, e.g. with another budget: from the sorted instances (sorting them again keeps them)
+    g->pos.release();  // the sort does not carry the positions
     const float extractMs = g->stats.ms[0];
     const int rc = build_edges_impl(g, pair_budget);
     g->stats.ms[0] = extractMs;
@@ -1093,5 +1489,184 @@ extern "C" int mtb_group_finish(mtb_grouper* g, uint32_t* group_map, mtb_group_s
         g->stats.ms[5 + p] = ms[p];
     }
     if (stats) *stats = g->stats;
+    return MTB_OK;
+}
+
+// ---- the common-k-mer filter's entry points -------------------------------------------------------
+extern "C" void mtb_group_filter_constants(uint32_t out[4]) {
+    if (!out) return;
+    out[0] = kSetLeaf;
+    out[1] = kSetTop;
+    out[2] = kNbrLdsBits;
+    out[3] = 0;
+}
+
+extern "C" int mtb_group_set_common_kmers(mtb_grouper* g, const uint64_t* values, uint64_t n) {
+    if (const int rc = attachable(g)) return rc;
+    if (n && !values) { set_error("null argument"); return MTB_ERR_ARG; }
+    GRP_TRY(hipSetDevice(g->device));
+    EvPair ev;
+    GRP_TRY(ev.create());
+    GRP_TRY(hipEventRecord(ev.a, nullptr));
+    uint64_t nSet = 0;
+    if (n) {
+        Buf dVal, flag, off, tmp, desc;
+        hipError_t e = dVal.alloc(8 * n);
+        if (e == hipSuccess) e = flag.alloc(4 * n);
+        if (e == hipSuccess) e = off.alloc(8 * (n + 1));
+        if (e == hipSuccess) e = tmp.alloc(8 * scan_tmp_elems(n));
+        if (e == hipSuccess) e = desc.alloc(4);
+        if (e != hipSuccess) GRP_SET_OOM(e, n * (8 + 4 + 8 + 8));
+        GRP_TRY(hipMemcpy(dVal.p, values, 8 * n, hipMemcpyHostToDevice));
+        GRP_TRY(hipMemset(desc.p, 0, 4));
+        bool descending = false;
+        if (const int rc = append_distinct(g->setVals, nSet, dVal.as<uint64_t>(), n, false, 0, flag.as<uint32_t>(),
+                                           off.as<uint64_t>(), tmp.p, desc.as<int>(), &descending))
+            return rc;
+        if (descending) { set_error("the common k-mer values descend"); return MTB_ERR_ARG; }
+    }
+    return finish_set(g, nSet, ev);
+}
+
+extern "C" int mtb_group_set_common_db(mtb_grouper* g, const char* db_dir) {
+    if (const int rc = attachable(g)) return rc;
+    if (!db_dir) { set_error("null argument"); return MTB_ERR_ARG; }
+    const std::string dir(db_dir);
+    int checked = 0;
+    if (const int rc = check_kmer_params(g, dir, &checked)) return rc;
+    FILE* f = fopen((dir + "/diffIdx").c_str(), "rb");
+    if (!f) { set_error("cannot open " + dir + "/diffIdx"); return MTB_ERR_IO; }
+    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
+    if (fseeko(f, 0, SEEK_END) != 0) { set_error("cannot size " + dir + "/diffIdx"); return MTB_ERR_IO; }
+    const uint64_t bytes = (uint64_t)ftello(f);
+    if (bytes % 2) { set_error("diffIdx ends mid k-mer"); return MTB_ERR_DB; }
+    const uint64_t nDiff = bytes / 2;
+    GRP_TRY(hipSetDevice(g->device));
+    EvPair ev;
+    GRP_TRY(ev.create());
+    GRP_TRY(hipEventRecord(ev.a, nullptr));
+    uint64_t nSet = 0;
+    if (nDiff) {
+        uint64_t W = 1ull << 26;  // words per chunk, as decode_db_chunked cuts the reference DB's
+        if (const char* e = getenv("MTB_DECODE_CHUNK_WORDS")) W = std::max<uint64_t>(8, strtoull(e, nullptr, 10));
+        W = std::min(W, nDiff);
+        Buf dDiff, dFlag, dIdx, dTmp, dVal, desc;
+        hipError_t e = dDiff.alloc(2 * W);
+        if (e == hipSuccess) e = dFlag.alloc(4 * W);
+        if (e == hipSuccess) e = dIdx.alloc(8 * (W + 2));
+        if (e == hipSuccess) e = dTmp.alloc(8 * scan_tmp_elems(W + 1));
+        if (e == hipSuccess) e = dVal.alloc(8 * W);
+        if (e == hipSuccess) e = desc.alloc(4);
+        if (e != hipSuccess) GRP_SET_OOM(e, W * (2 + 4 + 8 + 8 + 8));
+        GRP_TRY(hipMemset(desc.p, 0, 4));
+        std::vector<uint16_t> host(W);
+        uint64_t w0 = 0, carry = 0;
+        bool first = true;
+        while (w0 < nDiff) {
+            const uint64_t n = std::min(W, nDiff - w0);
+            if (fseeko(f, (off_t)(2 * w0), SEEK_SET) != 0 || fread(host.data(), 2, n, f) != n) {
+                set_error("cannot read " + dir + "/diffIdx");
+                return MTB_ERR_IO;
+            }
+            GRP_TRY(hipMemcpy(dDiff.p, host.data(), 2 * n, hipMemcpyHostToDevice));
+            uint64_t lastTerm = 0, lastValue = 0;
+            const uint64_t terms = decode_diff_chunk(dDiff.as<uint16_t>(), n, carry, dVal.as<uint64_t>(), dFlag.as<uint32_t>(),
+                                                     dIdx.as<uint64_t>(), dTmp.p, &lastTerm, &lastValue, nullptr);
+            GRP_TRY(hipGetLastError());
+            // no terminator in a whole chunk (a k-mer of more words than a chunk, or a cut tail), or a last word that ends none
+            if (terms == 0 || (w0 + n == nDiff && lastTerm != n - 1)) { set_error("diffIdx ends mid k-mer"); return MTB_ERR_DB; }
+            bool descending = false;
+            if (const int rc = append_distinct(g->setVals, nSet, dVal.as<uint64_t>(), terms, !first, carry, dFlag.as<uint32_t>(),
+                                               dIdx.as<uint64_t>(), dTmp.p, desc.as<int>(), &descending))
+                return rc;
+            if (descending) { set_error("diffIdx values descend"); return MTB_ERR_DB; }
+            first = false;
+            carry = lastValue;
+            w0 += lastTerm + 1;
+        }
+    }
+    g->fst.params_checked = checked;
+    return finish_set(g, nSet, ev);
+}
+
+extern "C" int mtb_group_get_filter_stats(mtb_grouper* g, mtb_group_filter_stats* out) {
+    if (!g || !out) { set_error("null argument"); return MTB_ERR_ARG; }
+    *out = g->fst;
+    return MTB_OK;
+}
+
+extern "C" int mtb_group_get_kmer_pos(mtb_grouper* g, uint32_t* pos, uint64_t cap, uint64_t* n) {
+    if (!g || !n) { set_error("null argument"); return MTB_ERR_ARG; }
+    if (!g->hasSet) { set_error("positions are kept only with a common k-mer set attached"); return MTB_ERR_ARG; }
+    if (g->built || (g->kmers && !g->pos.p)) { set_error("positions are released when the edges are built"); return MTB_ERR_ARG; }
+    *n = g->kmers;
+    if (cap < g->kmers) return MTB_RETRY;
+    if (!g->kmers) return MTB_OK;
+    if (!pos) { set_error("null argument"); return MTB_ERR_ARG; }
+    GRP_TRY(hipSetDevice(g->device));
+    GRP_TRY(hipMemcpy(pos, g->pos.p, 4 * g->kmers, hipMemcpyDeviceToHost));
+    return MTB_OK;
+}
+
+extern "C" int mtb_group_filter_common(int device, const uint64_t* db_values, uint64_t n_db, const uint64_t* values,
+                                       const uint32_t* read_ids, const uint32_t* pos, uint64_t n, uint8_t* hit,
+                                       uint8_t* keep) {
+    if ((n_db && !db_values) || (n && (!values || !read_ids || !pos || !hit || !keep))) {
+        set_error("null argument");
+        return MTB_ERR_ARG;
+    }
+    GRP_TRY(hipSetDevice(device));
+    DVec set(8);
+    Buf mid, top, desc;
+    SetIndex ix{};
+    uint64_t nSet = 0;
+    GRP_TRY(desc.alloc(4));
+    GRP_TRY(hipMemset(desc.p, 0, 4));
+    if (n_db) {
+        Buf dVal, flag, off, tmp;
+        GRP_TRY(dVal.alloc(8 * n_db));
+        GRP_TRY(flag.alloc(4 * n_db));
+        GRP_TRY(off.alloc(8 * (n_db + 1)));
+        GRP_TRY(tmp.alloc(8 * scan_tmp_elems(n_db)));
+        GRP_TRY(hipMemcpy(dVal.p, db_values, 8 * n_db, hipMemcpyHostToDevice));
+        bool descending = false;
+        if (const int rc = append_distinct(set, nSet, dVal.as<uint64_t>(), n_db, false, 0, flag.as<uint32_t>(), off.as<uint64_t>(),
+                                           tmp.p, desc.as<int>(), &descending))
+            return rc;
+        if (descending) { set_error("db_values descend"); return MTB_ERR_ARG; }
+    }
+    if (const int rc = build_set_index(ix, set.as<uint64_t>(), nSet, mid, top)) return rc;
+    if (!n) return MTB_OK;
+    Buf dKeys, dIds, dPos, flag, off, segStart, tmp, dHit, dRem;
+    GRP_TRY(dKeys.alloc(8 * n));
+    GRP_TRY(dIds.alloc(4 * n));
+    GRP_TRY(dPos.alloc(4 * n));
+    GRP_TRY(flag.alloc(4 * n));
+    GRP_TRY(off.alloc(8 * (n + 1)));
+    GRP_TRY(tmp.alloc(8 * scan_tmp_elems(n)));
+    GRP_TRY(dHit.alloc(n));
+    GRP_TRY(dRem.alloc(n));
+    GRP_TRY(hipMemcpy(dKeys.p, values, 8 * n, hipMemcpyHostToDevice));
+    GRP_TRY(hipMemcpy(dIds.p, read_ids, 4 * n, hipMemcpyHostToDevice));
+    GRP_TRY(hipMemcpy(dPos.p, pos, 4 * n, hipMemcpyHostToDevice));
+    // a segment per read: the heads of the runs of equal read IDs
+    k_flag_read_heads<<<stride_grid(n), 256>>>(dIds.as<uint32_t>(), n, flag.as<uint32_t>(), desc.as<int>());
+    int bad = 0;
+    GRP_TRY(hipMemcpy(&bad, desc.p, 4, hipMemcpyDeviceToHost));
+    if (bad) { set_error("read_ids descend"); return MTB_ERR_ARG; }
+    k_pos_range<<<stride_grid(n), 256>>>(dPos.as<uint32_t>(), n, desc.as<int>());
+    GRP_TRY(hipMemcpy(&bad, desc.p, 4, hipMemcpyDeviceToHost));
+    if (bad) { set_error("a pos of 2^31 or more"); return MTB_ERR_ARG; }
+    exclusive_scan_u32(flag.as<uint32_t>(), n, off.as<uint64_t>(), tmp.p, nullptr);
+    uint64_t nSeg = 0;
+    GRP_TRY(hipMemcpy(&nSeg, off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost));
+    GRP_TRY(segStart.alloc(8 * (nSeg + 1)));
+    k_head_pos<<<stride_grid(n + 1), 256>>>(flag.as<uint32_t>(), off.as<uint64_t>(), n, segStart.as<uint64_t>());
+    if (const int rc = run_filter(ix, dKeys.as<uint64_t>(), 0, dPos.as<uint32_t>(), segStart.as<uint64_t>(), 1, nSeg, n,
+                                  dHit.as<uint8_t>(), dRem.as<uint8_t>(), nullptr))
+        return rc;
+    GRP_TRY(hipMemcpy(hit, dHit.p, n, hipMemcpyDeviceToHost));
+    GRP_TRY(hipMemcpy(keep, dRem.p, n, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; i++) keep[i] = !keep[i];
     return MTB_OK;
 }

@@ -2,14 +2,15 @@
 mtb_group_* section of include/mtb_gpu.h.
 
 make_groups runs the three grouping phases (makeGroups, mergeBySupport at its defaults,
-makeGroupsPhase2) on an edge list and returns the groupMap after each phase.
+makeGroupsPhase2) on an edge list and returns the groupMap after each phase. filter_common runs the
+common-k-mer filter's kernels (filterCommonKmers) on instance arrays.
 """
 import ctypes
 import dataclasses
 
 import numpy as np
 
-from ._abi import RELATION_DTYPE, MtbGroupParams, MtbGroupStats
+from ._abi import RELATION_DTYPE, MtbGroupFilterStats, MtbGroupParams, MtbGroupStats
 from ._lib import check, lib
 
 
@@ -37,9 +38,9 @@ class GroupParams:
         return cls(**{f.name: getattr(p, f.name) for f in dataclasses.fields(cls)})
 
 
-def stats_dict(st: MtbGroupStats) -> dict:
+def stats_dict(st) -> dict:
     out = {}
-    for name, _ in MtbGroupStats._fields_:
+    for name, _ in st._fields_:
         v = getattr(st, name)
         out[name] = list(v) if hasattr(v, "__len__") else v
     return out
@@ -64,6 +65,31 @@ def make_groups(edges: np.ndarray, n_reads: int, total_kmers: int, par: GroupPar
                                       total_kmers, ctypes.byref(cp), maps.ctypes.data, ctypes.byref(st)),
           "mtb_group_make_groups")
     return maps, stats_dict(st)
+
+
+def filter_constants() -> dict:
+    """The sizes at which the filter's kernels change path (mtb_group_filter_constants)."""
+    c = (ctypes.c_uint32 * 4)()
+    lib().mtb_group_filter_constants(ctypes.byref(c))
+    return {"set_leaf": c[0], "set_top": c[1], "lds_bits": c[2]}
+
+
+def filter_common(db_values, values, read_ids, pos, device: int = 0):
+    """The common-k-mer filter on instance arrays in read order (read_ids non-descending) against the
+    ascending db_values: (hit, keep), bool arrays. An instance is hit iff its value is in db_values and
+    kept iff no hit of its read lies within one nucleotide of it."""
+    db = np.ascontiguousarray(db_values, np.uint64)
+    v = np.ascontiguousarray(values, np.uint64)
+    r = np.ascontiguousarray(read_ids, np.uint32)
+    p = np.ascontiguousarray(pos, np.uint32)
+    if not (len(v) == len(r) == len(p)):
+        raise ValueError("values, read_ids and pos differ in length")
+    hit, keep = np.zeros(len(v), np.uint8), np.zeros(len(v), np.uint8)
+    check(lib().mtb_group_filter_common(device, db.ctypes.data if len(db) else None, len(db),
+                                        v.ctypes.data if len(v) else None, r.ctypes.data if len(v) else None,
+                                        p.ctypes.data if len(v) else None, len(v), hit.ctypes.data if len(v) else None,
+                                        keep.ctypes.data if len(v) else None), "mtb_group_filter_common")
+    return hit.astype(bool), keep.astype(bool)
 
 
 def write_group_files(out_dir, group_map: np.ndarray) -> None:
@@ -122,6 +148,30 @@ class ReadGrouper:
 
     def __exit__(self, *exc):
         self.close()
+
+    def set_common_db(self, db_dir):
+        """Attach the common-k-mer DB at db_dir (its diffIdx, and kmer_params when present); before the
+        first batch, at most once."""
+        check(lib().mtb_group_set_common_db(self._h, str(db_dir).encode()), "mtb_group_set_common_db")
+
+    def set_common_kmers(self, values):
+        """Attach the common k-mers from an ascending array (repeats allowed, may be empty)."""
+        v = np.ascontiguousarray(values, np.uint64)
+        check(lib().mtb_group_set_common_kmers(self._h, v.ctypes.data if len(v) else None, len(v)),
+              "mtb_group_set_common_kmers")
+
+    def filter_stats(self) -> dict:
+        st = MtbGroupFilterStats()
+        check(lib().mtb_group_get_filter_stats(self._h, ctypes.byref(st)), "mtb_group_get_filter_stats")
+        return stats_dict(st)
+
+    def kmer_pos(self):
+        """pos of the instances kmers() returns (with a common-k-mer set, before build_edges)."""
+        n = ctypes.c_uint64()
+        check(lib().mtb_group_get_kmer_pos(self._h, None, 0, ctypes.byref(n)), "mtb_group_get_kmer_pos")
+        p = np.zeros(n.value, np.uint32)
+        check(lib().mtb_group_get_kmer_pos(self._h, p.ctypes.data, n.value, ctypes.byref(n)), "mtb_group_get_kmer_pos")
+        return p
 
     def add_batch(self, seq1, off1, seq2=None, off2=None, flags: int = 0):
         """A batch in mtb_classify_batch's flat layout (uint8 bases, n + 1 uint64 offsets), or device
@@ -190,10 +240,11 @@ class ReadGrouper:
 
 
 def group_reads(query1, query2, out_dir, par: GroupParams = None, device: int = 0, pair_budget: int = 0,
-                max_reads: int = 1 << 20, max_bases: int = 1 << 30):
+                max_reads: int = 1 << 20, max_bases: int = 1 << 30, common_db=None):
     """groupGeneration over FASTA / FASTQ files (plain or gzip): batches streamed through mtb_reader_*,
     the graph and the phases on the device; writes out_dir/groupMap, groups and skipped_kmers
-    ("value \\t m" per skipped k-mer). Returns (groupMap, stats)."""
+    ("value \\t m" per skipped k-mer). common_db: a common-k-mer DB directory; every batch then goes
+    through the common-k-mer filter and stats["filter"] holds its counts. Returns (groupMap, stats)."""
     import pathlib
 
     from ._abi import MtbReadBatch
@@ -207,6 +258,8 @@ def group_reads(query1, query2, out_dir, par: GroupParams = None, device: int = 
           "mtb_reader_open")
     try:
         with ReadGrouper(par, device) as g:
+            if common_db is not None:
+                g.set_common_db(common_db)
             batch = MtbReadBatch()
             while True:
                 check(L.mtb_reader_next(rd, max_reads, max_bases, ctypes.byref(batch)), "mtb_reader_next")
@@ -219,6 +272,8 @@ def group_reads(query1, query2, out_dir, par: GroupParams = None, device: int = 
             g.build_edges(pair_budget)
             sv, sm = g.skipped()
             gm, st = g.finish()
+            if common_db is not None:
+                st["filter"] = g.filter_stats()
     finally:
         L.mtb_reader_close(rd)
     write_group_files(out_dir, gm)
