@@ -210,7 +210,7 @@ struct mtb_ctx {
     // mtb_open_phases: seconds of the DB files' read, upload + K3 decode into records, AA directory,
     // probe lines, run index, taxonomy + species map, and the whole open
     double openS[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // [7]: the records' allocation (inside [1])
-    static constexpr int kNumStats = 20;
+    static constexpr int kNumStats = 22;
     uint64_t stats[kNumStats] = {};  // mtb_last_stats
     uint32_t chunkC = 1;  // K1 windows per unit of the last batch
     uint64_t stageRegion = 0;  // slots per staging region of mStage (grows to the largest seen)
@@ -1661,6 +1661,11 @@ static int classify_batch(mtb_ctx* c, const char* seq, const uint64_t* off, cons
         c->stats[12] = ps[kStatStripes];  // run-index fallbacks (gallop searches) of the probe join
         c->stats[16] = 0;
         for (uint32_t i = 0; i < kStatStripes; i++) c->stats[16] += ps[kStatStripes + 1 + i];  // K4S: DB records read
+        c->stats[20] = c->stats[21] = 0;
+        for (uint32_t i = 0; i < kStatStripes; i++) {
+            c->stats[20] += ps[kLoopStats + i];                 // k_join_uniform: queries on the lane loop
+            c->stats[21] += ps[kLoopStats + kStatStripes + i];  // ... and waves holding one
+        }
     }
     for (int k = 0; k < 4; k++) HIP_TRY(hipEventElapsedTime(&c->stageMs[k], c->ev[k], c->ev[k + 1]));
     HIP_TRY(hipEventElapsedTime(&c->stageMs[4], c->ev[0], c->ev[4]));

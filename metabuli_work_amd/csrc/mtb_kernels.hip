@@ -2202,8 +2202,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kLean 
 // so the block's four waves run their dependent read chains (run index, records, rank atomic) out of
 // step with each other (join 47.4 -> 42.9 ms per 3.33M-pair batch, profiles/r06/ab_k4_wave.json).
 // kExt (the context holds run-length lines, MTB_LINE_EXT=1): they are staged beside the probe lines.
+// R (round 12, MTB_JOIN_REG_RUN): a run of up to R records is held in registers — its records read in
+// one phase, selected from registers and, but for the position word, packed before the rank atomic; a
+// run of R + 1 .. kLongRun records reads its first R in the same phase and loops over the rest, so the
+// wave waits for it through one more record phase and the emit loop (loop_queries / loop_waves count
+// them).
 constexpr int kWaveLines = 16;
-template <bool kExt>
+constexpr int kJoinRegRun = 4;  // the default R
+template <bool kExt, int R>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8)))
 k_join_uniform(const uint64_t* __restrict__ qkey, const uint32_t* __restrict__ qslot, uint32_t C, uint64_t Q,
                const DbRec* __restrict__ db, uint64_t D, const int32_t* __restrict__ spOf, uint32_t maxTax,
@@ -2272,39 +2278,73 @@ k_join_uniform(const uint64_t* __restrict__ qkey, const uint32_t* __restrict__ q
         }
         const uint64_t n = hi - lo;
         const bool longq = n > kLongRun;
-        const bool small = live && n <= 2;
-        uint64_t v0 = 0, v1 = 0;
-        uint32_t t0 = 0, t1 = 0;
-        if (small && n) {  // the run's records (a random read moves a 128-B line: the second only if present)
-            const DbRec r0 = db[lo], r1 = n == 2 ? db[lo + 1] : DbRec{0, 0, 0};
-            v0 = (uint64_t)r0.hi << 32 | r0.lo;
-            v1 = (uint64_t)r1.hi << 32 | r1.lo;
-            t0 = r0.tax;
-            t1 = r1.tax;
+        const bool lane_run = live && !longq;  // the lane's own run: registers (n <= R) or the loop (R < n)
+        const bool small = lane_run && n <= (uint64_t)R;
+        const bool loopq = lane_run && n > (uint64_t)R;
+        // the run's first min(n, R) records, all in flight together (a random read moves a 128-B line: a
+        // record is read only if the run holds it; none at or past hi, which the clamp keeps <= D - 1).
+        // Only the value's low word (the 24 DNA bits) and the taxID are kept.
+        uint32_t dna[R], tax[R];
+#pragma unroll
+        for (int k = 0; k < R; k++) {
+            const DbRec rec = lane_run && (uint64_t)k < n ? db[lo + k] : DbRec{0, 0, 0};
+            dna[k] = rec.lo;
+            tax[k] = rec.tax;
         }
         const HamRows hr = hamming_rows(key);
-        uint32_t c = 0, thr = 0, s0 = 255, s1 = 255;
+        // a selected record's segment words, formed before the rank atomic: taxID | hamming sum << 24
+        // (of every held record: the selection reads the sums back from it) and DNA | right-end
+        // Hamming's high byte << 24; the low bytes of the R records share rehLo. The frame, and so the
+        // Hamming direction, comes from the slot alone.
+        uint32_t pu;
+        const uint32_t u = slot_unit(slot, C, pu);
+        const uint32_t r = u / upr, local = u - r * upr;
+        const bool rev = (((local >= 6u ? local - 6u : local) < 3u) != (kmerFormat == 2));
+        uint32_t wTax[R], wDna[R], rehLo = 0, minSum = 255;
+#pragma unroll
+        for (int k = 0; k < R; k++) {
+            const uint32_t s = lane_run && (uint64_t)k < n ? hamming_sum_rows(hr, dna[k]) : 255u;
+            minSum = min(minSum, s);
+            wTax[k] = (tax[k] & kSegMaxTax) | s << 24;  // a taxID past maxTax (<= kSegMaxTax) is refused below
+            wDna[k] = 0;
+        }
+        uint32_t c = 0, thr = min(minSum * 2u, 7u), sel = 0;
         if (small) {
-            s0 = n > 0 ? hamming_sum_rows(hr, v0) : 255u;
-            s1 = n > 1 ? hamming_sum_rows(hr, v1) : 255u;
-            thr = min(min(s0, s1) * 2u, 7u);
-            c = (uint32_t)(s0 <= thr) + (uint32_t)(s1 <= thr);
-        } else if (live && !longq) {
-            c = run_select(hr, dbv, 0, lo, hi, D, thr);
+#pragma unroll
+            for (int k = 0; k < R; k++) {
+                if ((wTax[k] >> 24) > thr) continue;
+                sel |= 1u << k;
+                const uint32_t reh = hammings_rows(hr, key, dna[k], rev);
+                wDna[k] = (dna[k] & 0xFFFFFFu) | (reh >> 8) << 24;
+                rehLo |= (reh & 0xFFu) << (8 * k);
+            }
+            c = (uint32_t)__popc(sel);
         }
         // the selected records' species (L2-resident spOf) in flight with the rank atomic below
-        const bool e0 = small && s0 <= thr, e1 = small && s1 <= thr;
-        const int32_t sp0 = e0 ? (t0 <= maxTax ? spOf[t0] : 0) : 0;
-        const int32_t sp1 = e1 ? (t1 <= maxTax ? spOf[t1] : 0) : 0;
-        uint32_t rk = 0, r = 0;
+        int32_t sp[R];
+#pragma unroll
+        for (int k = 0; k < R; k++) sp[k] = (sel >> k & 1u) && tax[k] <= maxTax ? spOf[tax[k]] : 0;
+        if (loopq) {  // run_select with the first R sums already tallied (n <= kLongRun: the tally's bytes hold it)
+            uint64_t tally = 0;
+#pragma unroll
+            for (int k = 0; k < R; k++)
+                if ((wTax[k] >> 24) <= 7u) tally += 1ull << (8 * (wTax[k] >> 24));
+            for (uint64_t t = lo + R; t < hi; t++) {
+                const uint32_t s = hamming_sum_rows(hr, dbv[t]);
+                minSum = min(minSum, s);
+                if (s <= 7) tally += 1ull << (8 * s);
+            }
+            thr = min(minSum * 2u, 7u);
+#pragma unroll
+            for (uint32_t s = 0; s < 8; s++)
+                if (s <= thr) c += (uint32_t)(tally >> (8 * s)) & 0xFFu;
+        }
+        uint32_t rk = 0;
         uint64_t info = 0;
         if (c) {
-            uint32_t p;
-            const uint32_t u = slot_unit(slot, C, p);
-            r = u / upr;
             const unsigned long long old = atomicAdd(&cnt64[r], (unsigned long long)c);
             rk = (uint32_t)old;
-            info = uniform_unit_info(u, p, upr, (uint32_t)(old >> 32), kmerFormat);
+            info = uniform_unit_info(u, pu, upr, (uint32_t)(old >> 32), kmerFormat);
         }
         const uint64_t lm = __ballot(longq && live);
         if (lm) {  // the wave's long queries to the long-run list (one atomic per wave), for k_match_long
@@ -2317,8 +2357,15 @@ k_join_uniform(const uint64_t* __restrict__ qkey, const uint32_t* __restrict__ q
         if (lane == 0 && hw) atomicAdd(&stats[tile % kStatStripes], (unsigned long long)__popcll(hw));
         const uint64_t gw = __ballot(gallop);
         if (gw && (threadIdx.x & 63) == 0) atomicAdd(&stats[kStatStripes], (unsigned long long)__popcll(gw));
+        // runs the lane loops over (R < n <= kLongRun) and the waves that hold one, on stripes of their own past
+        // the K4S stripes (with R = 2 nearly every wave holds one: on one word each the 24M atomics of a
+        // 3.33M-pair batch took 240 ms)
+        const uint64_t lw = __ballot(loopq);
+        if (lane == 0 && lw) {
+            atomicAdd(&stats[kLoopStats + tile % kStatStripes], (unsigned long long)__popcll(lw));
+            atomicAdd(&stats[kLoopStats + kStatStripes + tile % kStatStripes], 1ull);
+        }
         if (!c) return;
-        const bool rev = ((info_frame(info) < 3) != (kmerFormat == 2));
         // the read's stretch of upr units (C slots each) bounds its segment; ranks past it spill to buf
         const uint64_t cap = ((uint64_t)upr * C) >> capShift;
         const bool spill = rk + c > cap;
@@ -2333,26 +2380,25 @@ k_join_uniform(const uint64_t* __restrict__ qkey, const uint32_t* __restrict__ q
         }
         SegMatch* const out = direct + (uint64_t)r * upr * C;
         if (small) {
-    #pragma unroll
-            for (int k = 0; k < 2; k++) {
-                if (!(k ? e1 : e0)) continue;
-                const uint64_t tv = k ? v1 : v0;
-                const uint32_t tax = k ? t1 : t0, hs = k ? s1 : s0;
-                const int32_t sp = k ? sp1 : sp0;
-                if (tax == 0 || sp <= 0) atomicExch(err, kErrTaxid);  // KmerMatcher.cpp:432-441 exits
-                mtb_match m;
-                m.qinfo = info;
-                m.target_id = tax;
-                m.species_id = (uint32_t)sp;
-                m.dna_encoding = (uint32_t)(tv & 0xFFFFFFull);
-                m.right_end_hamming = (uint16_t)hammings_rows(hr, key, tv, rev);
-                m.hamming = (uint8_t)hs;
-                m.pad = 0;
+            const uint32_t posFrame = (uint32_t)info | (uint32_t)(info >> 61) << 29;  // seg_pack's first word
+#pragma unroll
+            for (int k = 0; k < R; k++) {
+                if (!(sel >> k & 1u)) continue;
+                const uint32_t t = wTax[k] & kSegMaxTax, lowReh = rehLo >> (8 * k) & 0xFFu;
+                if (t == 0 || sp[k] <= 0) atomicExch(err, kErrTaxid);  // KmerMatcher.cpp:432-441 exits
                 if (spill) {
+                    mtb_match m;
+                    m.qinfo = info;
+                    m.target_id = t;
+                    m.species_id = (uint32_t)sp[k];
+                    m.dna_encoding = wDna[k] & 0xFFFFFFu;
+                    m.right_end_hamming = (uint16_t)(lowReh | (wDna[k] >> 24) << 8);
+                    m.hamming = (uint8_t)(wTax[k] >> 24);
+                    m.pad = 0;
                     bufRank[w] = rk++;
                     buf[w] = m;
                 } else {
-                    out[w] = seg_pack(m);
+                    out[w] = SegMatch{posFrame, wTax[k], (uint32_t)sp[k] | lowReh << 24, wDna[k]};
                 }
                 w++;
             }
@@ -3179,14 +3225,27 @@ void launch_match(const uint64_t* qkey, const uint32_t* qslot, const uint64_t* u
         const char* fe = getenv("MTB_JOIN_FAST");
         const bool fastOk = (!fe || atoi(fe) != 0) && lines && runOff && direct && longList && upr && cnt64;
         const bool ext = runOff && lineExt;  // run-length lines (MTB_LINE_EXT=1) staged beside the probe lines
+        // MTB_JOIN_REG_RUN=2|3|4 (A/B, read per batch): the longest run k_join_uniform holds in registers
+        int regRun = kJoinRegRun;
+        if (const char* re = getenv("MTB_JOIN_REG_RUN")) {
+            const int v = atoi(re);
+            if (v >= 2 && v <= 4) {
+                regRun = v;
+            } else {
+                static bool told = false;  // said once: a value no instance exists for keeps the default
+                if (!told) fprintf(stderr, "[mtb] MTB_JOIN_REG_RUN=%s is not 2, 3 or 4: using %d\n", re, kJoinRegRun);
+                told = true;
+            }
+        }
+        auto joinUniform = [&](auto kernel) {
+            kernel<<<(unsigned)((Q + 255) / 256), 256, 0, s>>>(
+                qkey, qslot, C, Q, db, D, spOf, maxTax, kmerFormat, total, buf, bufRank, region, err, lines, lineP, runOff,
+                sortLo, stats, direct, overflow, capShift, longList, longCap, longCnt, upr, cnt64, ext ? lineExt : nullptr);
+        };
         if (fastOk && ext)
-            k_join_uniform<true><<<(unsigned)((Q + 255) / 256), 256, 0, s>>>(
-                qkey, qslot, C, Q, db, D, spOf, maxTax, kmerFormat, total, buf, bufRank, region, err, lines, lineP, runOff,
-                sortLo, stats, direct, overflow, capShift, longList, longCap, longCnt, upr, cnt64, lineExt);
+            joinUniform(regRun == 2 ? k_join_uniform<true, 2> : regRun == 3 ? k_join_uniform<true, 3> : k_join_uniform<true, 4>);
         else if (fastOk)
-            k_join_uniform<false><<<(unsigned)((Q + 255) / 256), 256, 0, s>>>(
-                qkey, qslot, C, Q, db, D, spOf, maxTax, kmerFormat, total, buf, bufRank, region, err, lines, lineP, runOff,
-                sortLo, stats, direct, overflow, capShift, longList, longCap, longCnt, upr, cnt64, nullptr);
+            joinUniform(regRun == 2 ? k_join_uniform<false, 2> : regRun == 3 ? k_join_uniform<false, 3> : k_join_uniform<false, 4>);
         else if (ext)
             k_match<false, false><<<blocks, 256, 0, s>>>(qkey, qslot, unitInfo, C, Q, db, D, dir, spOf, maxTax, kmerFormat,
                                                          readCnt, total, buf, bufRank, region, err, winCap, win, lines,

@@ -188,8 +188,10 @@ struct alignas(64) ProbeLine {
 };
 static_assert(sizeof(ProbeLine) == 64, "one probe line per 64-B segment");
 constexpr uint32_t kStatStripes = 256;
-// join statistics: [0, 256) matched-query stripes, [256] gallop fallbacks, [257, 513) K4S DB-record stripes
-constexpr uint32_t kProbeStatsLen = 2 * kStatStripes + 1;
+// join statistics: [0, 256) matched-query stripes, [256] gallop fallbacks, [257, 513) K4S DB-record stripes,
+// [513, 769) k_join_uniform's loop-path queries (runs longer than its registers hold), [769, 1025) waves holding one
+constexpr uint32_t kLoopStats = 2 * kStatStripes + 1;
+constexpr uint32_t kProbeStatsLen = 4 * kStatStripes + 1;
 constexpr uint64_t kDbPad = 8;  // ~0 values after the resident DB
 constexpr uint64_t kProbeLines = (kAARankEnd + kLineRanks - 1) / kLineRanks + 1;  // + an end line (base D)
 void build_probe_lines(const DbRec* db, uint64_t D, const AADir& dir, ProbeLine* lines,
