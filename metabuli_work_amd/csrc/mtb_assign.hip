@@ -2684,6 +2684,33 @@ __device__ __forceinline__ mtb_result empty_result(int readLength) {
     return res;
 }
 
+// The tie set's score sum under --em. There the reference sorts sp2score by score, descending, before
+// the loop that adds up the tie set (Taxonomer.cpp:377-394), so its float additions run from the
+// largest score down and not in species order; from three unequal scores on the two orders can round
+// differently. Equal scores commute, so the sort's tie order does not show in the sum: the distinct
+// scores of the set are taken from the top down, each added as often as it occurs. Every lane that
+// calls it computes the same value from the same global reads. Cost: one pass over the read's species
+// runs per distinct score of the set, repeated by every lane of the wave or group that holds the
+// read. That is accepted because it runs only under --em and only for a tie set of three or more.
+__device__ float em_tie_sum(const float* __restrict__ spScore, const uint8_t* __restrict__ spKeep, uint64_t s0,
+                            uint64_t s1, float thr) {
+    float total = 0.0f, prev = INFINITY;
+    while (true) {
+        float v = 0.0f;
+        long k = 0;
+        for (uint64_t s = s0; s < s1; s++) {
+            if (!spKeep[s]) continue;
+            const float x = spScore[s];
+            if (!(x >= thr) || !(x < prev)) continue;
+            if (k == 0 || x > v) { v = x; k = 1; }
+            else if (x == v) k++;
+        }
+        if (k == 0) return total;
+        for (long i = 0; i < k; i++) total += v;
+        prev = v;
+    }
+}
+
 // chooseBestTaxon (Taxonomer.cpp:130-202), filterRedundantMatches (:205-241), taxCnt and the
 // lower-rank BFS (:252-314): one thread per read (short reads).
 __global__ void __launch_bounds__(256) k_choose_taxon(const mtb_match* __restrict__ M, const uint64_t* __restrict__ mOff,
@@ -2738,6 +2765,7 @@ __global__ void __launch_bounds__(256) k_choose_taxon(const mtb_match* __restric
         if (cnt > 1) {
             isLCA = true;
             bestTax = lcaNode >= 0 ? tax.nodeTax[lcaNode] : 0;
+            if (cfg.em && cnt > 2) spTotal = em_tie_sum(spScore, spKeep, s0, s1, thr);
             spTotal = spTotal / (float)cnt;
         }
     }
@@ -2762,7 +2790,8 @@ __global__ void __launch_bounds__(256) k_choose_taxon(const mtb_match* __restric
 
 // The same for reads with many matches (long reads): one wave per read. The species-run scan is
 // spread over the lanes (sum / max reductions, the first maximum by ballot; the tie set summed in
-// species order, as the reference's float additions run); filterRedundantMatches is a parallel
+// species order, as the reference's float additions run; from the largest score down under --em,
+// em_tie_sum); filterRedundantMatches is a parallel
 // reduction over a per-quotient table in LDS (atomicMin of the hamming, then LCA folds of the
 // minimal matches' taxa by compare-and-swap: an order-free reduction, as the serial fold is), and
 // taxCnt a small LDS hash of (taxon, count). Reads whose quotients or distinct taxa do not fit take
@@ -2864,6 +2893,7 @@ __global__ void __launch_bounds__(64) k_choose_taxon_wave(const mtb_match* __res
         if (cnt > 1) {
             isLCA = true;
             bestTax = lcaNode >= 0 ? tax.nodeTax[lcaNode] : 0;
+            if (cfg.em && cnt > 2) spTotal = em_tie_sum(spScore, spKeep, s0, s1, thr);
             spTotal = spTotal / (float)cnt;
         }
     }
@@ -3074,6 +3104,7 @@ __global__ void __launch_bounds__(256) k_choose_taxon_group(const mtb_match* __r
             if (cnt > 1) {
                 isLCA = true;
                 bestTax = lcaNode >= 0 ? tax.nodeTax[lcaNode] : 0;
+                if (cfg.em && cnt > 2) spTotal = em_tie_sum(spScore, spKeep, s0, s1, thr);
                 spTotal = spTotal / (float)cnt;
             }
         }

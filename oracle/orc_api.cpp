@@ -78,6 +78,7 @@ void* orc_db_open(const char* dir, char* err, int errlen) {
         delete db;
         return nullptr;
     }
+    db->dbDir = d;
     return db;
 }
 

@@ -26,6 +26,7 @@ struct Db {
     std::vector<TaxID> taxIdList;
     Taxonomy tax;
     std::unordered_map<TaxID, TaxID> taxId2speciesId;
+    std::string dbDir;  // the directory the DB was opened from ("" for an in-memory DB): --em's sp2uniqKmerCnt
     bool buildSpeciesMap(std::string* err);
 };
 

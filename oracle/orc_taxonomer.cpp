@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <fstream>
 #include <limits>
 
 #include "orc_internal.h"
@@ -458,12 +459,23 @@ void assignTaxonomy(const Db& db, const mtb_params& par, const mtb_match* matchL
 namespace orc {
 
 void emReassign(const Db& db, const mtb_em_map* maps, size_t n, size_t totalQueryCnt, EmOut& out) {
-    // countUniqueKmerPerSpecies (Classifier.cpp:388-431): every info entry's species
+    // countUniqueKmerPerSpecies (Classifier.cpp:388-431): dbDir/sp2uniqKmerCnt when present ("taxID
+    // count" pairs; a taxID past the vector of maxTaxID + 1 entries is skipped, :403-409), else every
+    // info entry's species. The reference also writes the file after counting; the oracle does not.
     std::unordered_map<TaxID, uint32_t> sp2uniq;
-    for (uint32_t t : db.info) {
-        if (t == 0) break;  // ReadBuffer<TaxID>::getNext() == 0 ends the loop
-        auto it = db.taxId2speciesId.find((TaxID)t);
-        if (it != db.taxId2speciesId.end() && it->second) sp2uniq[it->second]++;
+    std::ifstream cntFile;
+    if (!db.dbDir.empty()) cntFile.open(db.dbDir + "/sp2uniqKmerCnt");
+    if (cntFile.is_open()) {
+        TaxID t;
+        uint32_t count;
+        while (cntFile >> t >> count)
+            if (t >= 0 && t <= db.tax.maxTaxID) sp2uniq[t] = count;
+    } else {
+        for (uint32_t t : db.info) {
+            if (t == 0) break;  // ReadBuffer<TaxID>::getNext() == 0 ends the loop
+            auto it = db.taxId2speciesId.find((TaxID)t);
+            if (it != db.taxId2speciesId.end() && it->second) sp2uniq[it->second]++;
+        }
     }
     auto lengthFactor = [&](TaxID sp) {
         auto it = sp2uniq.find(sp);

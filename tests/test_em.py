@@ -10,11 +10,15 @@ The oracle restates all of it on one thread; a pure-Python restatement below che
 EM (CPU). The GPU tests hold the device mappings and results to the oracle bit for bit, the
 device EM to the oracle's (abundances within 1e-12 relative: the device sums large species in
 fixed slices, the reference's OpenMP sums in thread order, so no bitwise order exists), and the
-native pipeline's EM files to the oracle's. Parity unpinned beyond the restatements (no reference
-fixtures for --em).
+native pipeline's EM files to the oracle's. The per-read part (results under em and the species2Score
+lists) is pinned to the reference's own Taxonomer by tests/golden/ref_assign.npz's em parameter sets
+(tests/test_ref_assign.py, oracle and device); Classifier::em and reclassify have no reference fixture
+and stay restatements (designed inputs, bit for bit: tests/test_em_designed.py).
 """
 import collections
 import math
+import os
+import shutil
 
 import numpy as np
 import pytest
@@ -31,6 +35,15 @@ def _par(db_dir, kind, em=1):
     par = LocalParameters(seqMode=SEQ_MODE[kind], em=em)
     par.load_db_parameters(db_dir)
     return par
+
+
+def _pristine(db_dir, tmp_path):
+    """A copy of the DB without sp2uniqKmerCnt, for the oracle. mtb_em writes that file next to the DB
+    it was opened on and the oracle reads it when present; on the copy the oracle counts the species'
+    k-mers from `info` itself, so its EM stays an independent check of k_species_kmers."""
+    d = str(tmp_path / "oracle_db")
+    shutil.copytree(db_dir, d, ignore=shutil.ignore_patterns("sp2uniqKmerCnt"))
+    return d
 
 
 def _batches(gen, kind, seed, sizes):
@@ -149,6 +162,12 @@ def _sp_kmers(db_dir, tax):
     return cnt
 
 
+def _count_file_text(db_dir, tax):
+    """What countUniqueKmerPerSpecies writes into sp2uniqKmerCnt (Classifier.cpp:413-430): a
+    "taxID count" line per species with DB k-mers, in taxID order."""
+    return "".join(f"{s} {k}\n" for s, k in sorted(_sp_kmers(db_dir, tax).items()) if k > 0)
+
+
 def _check_maps(maps, results):
     """Per query: <= 10 mappings, scores (squares) non-increasing; classified reads only."""
     ores = np.concatenate([r[0] for r in results])
@@ -161,11 +180,12 @@ def _check_maps(maps, results):
 
 
 @pytest.mark.parametrize("db_name,kind", [("fmt2_acc", "paired"), ("fmt2", "long")])
-def test_oracle_em_against_python(make_db, db_name, kind):
-    """CPU: the oracle's EM and reassignment equal an independent Python restatement."""
+def test_oracle_em_against_python(make_db, tmp_path, db_name, kind):
+    """CPU: the oracle's EM and reassignment equal an independent Python restatement (the oracle's own
+    count from `info`: _pristine)."""
     db_dir, taxo, gen = make_db(db_name)
     par = _par(db_dir, kind)
-    odb = oc.OracleDb(db_dir)
+    odb = oc.OracleDb(_pristine(db_dir, tmp_path))
     maps, results, total = _oracle_maps(odb, par, _batches(gen, kind, 71, [300, 200] if kind != "long" else [20, 15]))
     assert len(maps) > 0
     _check_maps(maps, results)
@@ -186,12 +206,13 @@ def test_oracle_em_against_python(make_db, db_name, kind):
 @pytest.mark.gpu
 @pytest.mark.parametrize("db_name,kind", [("fmt2_acc", "paired"), ("fmt2", "single"), ("fmt2_syncmer", "paired"),
                                           ("fmt1_acc", "paired"), ("fmt2", "long")])
-def test_em_device(make_db, db_name, kind):
+def test_em_device(make_db, tmp_path, db_name, kind):
     """Device --em: per-batch results and mappings bit-exact vs the oracle; mtb_em vs the oracle's
-    EM on the same mappings."""
+    EM on the same mappings. The oracle works on a copy without the count file (_pristine), and the
+    file the device leaves next to its DB holds the counts made here from `info` and the taxonomy."""
     db_dir, taxo, gen = make_db(db_name)
     par = _par(db_dir, kind)
-    odb = oc.OracleDb(db_dir)
+    odb = oc.OracleDb(_pristine(db_dir, tmp_path))
     batches = _batches(gen, kind, 81, [400, 250] if kind != "long" else [25, 15])
     maps, results, total = _oracle_maps(odb, par, batches)
     gmaps, off = [], 0
@@ -216,6 +237,7 @@ def test_em_device(make_db, db_name, kind):
     assert np.array_equal(g_reads["tax_id"], o_reads["tax_id"])
     assert np.array_equal(g_reads["mapped"], o_reads["mapped"])
     assert np.allclose(g_reads["score"], o_reads["score"], rtol=1e-12, atol=0)
+    assert open(os.path.join(db_dir, "sp2uniqKmerCnt")).read() == _count_file_text(db_dir, _Tax(taxo))
 
 
 @pytest.mark.gpu
@@ -251,7 +273,7 @@ def test_start_classify_em(make_db, tmp_path):
                                  em_reclassify_report_tsv=rc_rep) == r.n
         assert clf.last_run["batches"] == 3
         lineage = {t: clf.lineage(t) for t in taxo.taxid.tolist()}
-    odb = oc.OracleDb(db_dir)
+    odb = oc.OracleDb(_pristine(db_dir, tmp_path))  # the oracle counts the species' k-mers itself
     maps, results, total = _oracle_maps(odb, par, [synth.Reads(r.seq1, r.off1, r.seq2, r.off2, r.origin)])
     o_reads, o_sp, o_st = oc.em(odb, maps, total)
     ores = results[0][0]

@@ -7,7 +7,8 @@ lowerRankClassification / getSpeciesCladeCounts / BFS, Taxonomer.cpp:130-648) re
 four parameter sets, over the taxonomy make_db builds; and for compareDna (KmerMatcher.cpp:1117-1146)
 the selected candidates of 720 candidate lists. The oracle's restatements are compared with it
 exactly (scores bitwise), and so is the device's K5 / K6 (both entry points, default and general
-paths), directly against the fixture, not the oracle.
+paths), directly against the fixture, not the oracle; under the em parameter sets also the mappings
+(species2Score lists) of both.
 
 `fmt2_acc_blank` is the fmt2_acc taxonomy with the strains' rank strings emptied (the leaf removal of
 rank "" at accessionLevel 2); make_db builds no such taxonomy, so oracle and device run over a copy
@@ -86,6 +87,17 @@ def compare_to_fixture(res, tc, want, ql, hamming=True):
         b = want["tc"][off[i]:off[i + 1]]
         assert np.array_equal(a["tax_id"], b[:, 0]) and np.array_equal(a["count"], b[:, 1].astype(np.uint32)), \
             f"read {i}: taxcnt {a} != {b}"
+
+
+def _compare_em_lists(maps, g, db, k, want):
+    """The device's --em mappings against the reference's species2Score lists, with the three
+    equalities test_oracle_assign_pinned holds the oracle to (classified reads only: writeMappings)."""
+    ln, lst = g[f"{db}_p{k}_s2_len"], g[f"{db}_p{k}_s2"]
+    keep = np.repeat(want["is_classified"].astype(bool), ln)
+    assert np.array_equal(maps["query_id"], np.repeat(np.arange(len(ln)), ln)[keep])
+    assert np.array_equal(maps["species_id"], lst[keep, 0])
+    assert np.array_equal(maps["score"].view(np.uint32), lst[keep, 1].astype(np.uint32))
+    assert ln[want["is_classified"].astype(bool)].sum() > 0 and _offsets(ln)[-1] == len(lst)
 
 
 def _blank_db(src, dst):
@@ -175,19 +187,22 @@ def test_device_assign_pinned(db_dir_of, db):
     old = os.environ.get("MTB_FORCE_GENERIC")
     try:
         for k, p in enumerate(params_of(g, db)):
-            if p["em"]:
-                continue  # the em lists are checked on the oracle only
             want = _fixture_results(g, db, k)
             for generic in ("0", "1"):
                 os.environ["MTB_FORCE_GENERIC"] = generic  # read when the context opens
                 par = LocalParameters(seqMode=p["seqMode"], minScore=fl(p["minScoreBits"]),
-                                      minSpScore=fl(p["minSpScoreBits"]), accessionLevel=int(p["accessionLevel"] == 1))
+                                      minSpScore=fl(p["minSpScoreBits"]), accessionLevel=int(p["accessionLevel"] == 1),
+                                      em=p["em"])
                 with Classifier(par, db_dir=db_dir) as clf:
                     assert clf.par.accessionLevel == p["accessionLevel"] and clf.par.kmerFormat == p["kmerFormat"]
                     ar = clf.assign_chunks(m, len(m), counts, 1, ql, n)
                     compare_to_fixture(ar.results, ar.taxcnt, want, ql, hamming=False)
+                    if p["em"]:
+                        _compare_em_lists(clf.em_mappings(), g, db, k, want)
                     br = clf.assign_matches(shuffled, ql)
                     compare_to_fixture(br.results, br.taxcnt, want, ql, hamming=False)
+                    if p["em"]:
+                        _compare_em_lists(clf.em_mappings(), g, db, k, want)
     finally:
         if old is None:
             os.environ.pop("MTB_FORCE_GENERIC", None)
