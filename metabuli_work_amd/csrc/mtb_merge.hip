@@ -10,6 +10,7 @@
 // The reference's pass-by-pass buffering (the `max` cut-offs) is a memory device of its own and
 // does not change the result; here everything is resident.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <filesystem>
 #include <fstream>
@@ -299,7 +300,9 @@ int merge_core(const mtb_merge_input* in, int nIn, const HostDb& db, const mtb_p
         N += in[i].n_info;
         maxWords = std::max(maxWords, in[i].n_diff_idx);
     }
-    const uint64_t W = std::max<uint64_t>(std::min<uint64_t>(maxWords, 1ull << 27), 1);  // words per decode chunk
+    uint64_t W = 1ull << 27;  // words per decode chunk
+    if (const char* e = getenv("MTB_DECODE_CHUNK_WORDS")) W = std::max<uint64_t>(8, strtoull(e, nullptr, 10));
+    W = std::max<uint64_t>(std::min(W, maxWords), 1);
     HIP_M(hipSetDevice(device));
     {
         size_t freeB = 0, totalB = 0;
