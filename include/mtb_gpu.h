@@ -411,6 +411,29 @@ int mtb_merge_last_ms(float* ms, int n);
 /* Items per merge tile (so tests can straddle it). */
 uint32_t mtb_merge_tile_items(void);
 
+/* The common-k-mer DB of read grouping (the reference's create_common_kmer_list,
+ * IndexCreator::createCommonKmerIndex), built on the GPU: the AA 12-mers of all six frames of every
+ * genome (extractKmer_dna2aa; with syncmer = 1 the syncmers of smer_len), and of their distinct values
+ * those that genomes of two or more species hold, ascending, info = the taxID of the LCA of those
+ * species (mergeTargetFiles<COMMON_KMER>). The rule is applied however the genomes were batched; the
+ * reference's one-flush build, which skips it, is not reproduced. diffIdx / info / split as
+ * mtb_merge_db encodes them with the whole value as the AA part (kmer_format 3, or 5 with syncmers),
+ * sizeOfSplit = (distinct (value, species) pairs) / (split_num - 1); taxid_list = the genomes' taxIDs,
+ * ascending. in: n_blocks must be 0 (whole genomes; the blk_* arrays are not read), split_num >= 2,
+ * flags MTB_INPUT_DEVICE or 0, else MTB_ERR_ARG; MTB_ERR_ARG for a smer_len outside [5, 12] with
+ * syncmers; MTB_ERR_DB for a genome whose taxID has no species in the taxonomy; MTB_ERR_OOM (the
+ * bytes needed in mtb_last_error) when one batch or a fold does not fit the device. */
+int mtb_build_common_db(const mtb_build_input* in, const mtb_db_host* taxonomy, int syncmer, int smer_len,
+                        int device, mtb_db_built* out);              /* release with mtb_free_built */
+
+/* Phase times of this process's last common-k-mer build in ms: [0] extraction, [1] sort,
+ * [2] reduce (per-batch dedupe + the final segmented reduction), [3] fold (merges), [4] encode + split,
+ * [5] total (HIP events). Returns the entries written. */
+int mtb_common_last_ms(float* ms, int n);
+
+/* Windows per extraction unit of the genome path (so tests can straddle it). */
+uint32_t mtb_common_unit_windows(void);
+
 /* ---- host I/O around the path ------------------------------------------ */
 /* One batch of reads in the flat layout mtb_classify_batch takes; names are the header's first
  * token (kseq), concatenated, name i = names[name_off[i] .. name_off[i+1]). Buffers belong to the

@@ -31,6 +31,7 @@ EXPORTED = [
     "mtb_group_get_kmers", "mtb_group_build_edges", "mtb_group_get_edges", "mtb_group_get_skipped", "mtb_group_finish",
     "mtb_group_set_common_db", "mtb_group_set_common_kmers", "mtb_group_get_filter_stats", "mtb_group_get_kmer_pos",
     "mtb_group_filter_common", "mtb_group_filter_constants",
+    "mtb_build_common_db", "mtb_common_last_ms", "mtb_common_unit_windows",
 ]
 
 
@@ -112,6 +113,9 @@ def lib() -> ctypes.CDLL:
     L.mtb_merge_last_ms.argtypes = [P(ctypes.c_float), i32]
     L.mtb_merge_tile_items.argtypes = []
     L.mtb_merge_tile_items.restype = u32
+    L.mtb_common_last_ms.argtypes = [P(ctypes.c_float), i32]
+    L.mtb_common_unit_windows.argtypes = []
+    L.mtb_common_unit_windows.restype = u32
     L.mtb_group_default_params.argtypes = [P(MtbGroupParams)]
     L.mtb_group_default_params.restype = None
     L.mtb_group_make_groups.argtypes = [i32, vp, u64, u32, u64, P(MtbGroupParams), vp, P(MtbGroupStats)]

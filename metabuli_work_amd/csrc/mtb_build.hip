@@ -182,14 +182,16 @@ __global__ void k_write_words(const uint64_t* __restrict__ uval, uint64_t U, con
     }
 }
 
+// aaShift: the bits below AminoAcidPart (IndexCreator.h:209-214): 24 DNA bits in formats 1 and 2, none
+// in formats 3 and 5, where the AA part is the whole value
 __global__ void k_split_ends(const uint64_t* __restrict__ uval, uint64_t U, uint64_t sizeOfSplit, int splitNum,
-                             uint64_t* __restrict__ gend) {
+                             int aaShift, uint64_t* __restrict__ gend) {
     int k = blockIdx.x * blockDim.x + threadIdx.x + 1;  // boundaries 1 .. splitNum-1
     if (k >= splitNum) return;
     uint64_t cnt = (uint64_t)k * sizeOfSplit;  // writeCnt that hits offsetList[k]
     if (sizeOfSplit == 0 || cnt == 0 || cnt > U) { gend[k - 1] = U; return; }
     uint64_t i = cnt - 1;
-    uint64_t key = (uval[i] & kAAMask) + (1ull << 24);
+    uint64_t key = ((uval[i] >> aaShift) + 1) << aaShift;
     uint64_t lo = i + 1, hi = U;
     while (lo < hi) {
         uint64_t mid = lo + ((hi - lo) >> 1);
@@ -276,7 +278,9 @@ int encode_sorted_kmers(const uint64_t* sk, const uint64_t* sp_, uint64_t kept, 
     // uniqKmerCnt / (splitNum - 1) in a build, numOfKmerBeforeMerge / (splitNum - 1) in a merge
     sizeOfSplit = splitNum > 1 ? (splitTotal == kSplitByUnique ? U : splitTotal) / (uint64_t)(splitNum - 1) : 0;
     HIP_B(hipMalloc(&gend, 8 * (size_t)std::max(1, splitNum)));
-    if (splitNum > 1) k_split_ends<<<(splitNum + 255) / 256, 256, 0, s>>>(uval, U, sizeOfSplit, splitNum, gend);
+    if (splitNum > 1)
+        k_split_ends<<<(splitNum + 255) / 256, 256, 0, s>>>(uval, U, sizeOfSplit, splitNum,
+                                                            kmerFormat == 3 || kmerFormat == 5 ? 0 : 24, gend);
     ge.assign((size_t)std::max(0, splitNum - 1), U);
     if (!ge.empty()) HIP_B(hipMemcpyAsync(ge.data(), gend, 8 * ge.size(), hipMemcpyDeviceToHost, s));
     out->n_diff_idx = NW;

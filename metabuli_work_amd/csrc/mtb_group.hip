@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "mtb_aa12.h"
 #include "mtb_host.h"
 #include "mtb_launch.h"
 
@@ -331,15 +332,6 @@ extern "C" int mtb_group_make_groups(int device, const mtb_relation* edges, uint
 // ------------------------------------------------------------------------------------------------
 namespace mtb {
 
-constexpr uint32_t kGroupChunk = 32;   // windows per extraction unit
-constexpr int kGroupK = 12;            // AA k-mer length
-constexpr uint64_t kAA12Mask = (1ull << 60) - 1;
-
-struct GroupTables {
-    uint8_t base[256];
-    int8_t aa[64];
-};
-
 // 12-mer windows per frame of each mate (0, 0 when the shared empty-read rule drops the read:
 // KmerExtractor.cpp:451-494 with kmerLen 12) and the read's units: chunks of kGroupChunk windows per
 // (mate, frame).
@@ -360,12 +352,8 @@ __global__ void k_group_units(const ReadMeta* __restrict__ meta, uint32_t n, int
     }
 }
 
-// One thread per unit: a chunk of <= kGroupChunk consecutive windows of one (read, mate, frame), after
-// 11 warm-up codons (a window depends on its own 12 codons only). Codons are read left to right on a
-// forward frame and from the right end on the complement for a reverse frame, as K1's format 2. A
-// window is kept iff its 12 codons translate and, with syncmers, the earliest minimum of its
-// 12 - s + 1 s-mers sits at either end (the deque of SyncmerScanner_dna2aa pops strictly greater
-// values only, so its front is the earliest minimum). Slot u * kGroupChunk + p holds window p of unit
+// One thread per unit: a chunk of <= kGroupChunk consecutive windows of one (read, mate, frame),
+// scanned by scan_aa12_chunk (mtb_aa12.h), frames as K1's format 2. Slot u * kGroupChunk + p holds window p of unit
 // u: (key, global read ID), or the sentinel. Units are in read order, so slot order is ascending in
 // read ID — the order the stable sort keeps within a key.
 __global__ void __launch_bounds__(256) k_extract_aa12(const uint8_t* __restrict__ seq1, const uint64_t* __restrict__ off1,
@@ -402,11 +390,6 @@ __global__ void __launch_bounds__(256) k_extract_aa12(const uint8_t* __restrict_
     if (fwd) begin = frame;
     else { begin = (len % 3) - (frame % 3); if (begin < 0) begin += 3; }
     const int s0 = begin, e0 = begin + used - 1;
-    const int nSm = kGroupK - smerLen + 1;
-    const uint64_t smMask = (1ull << (5 * smerLen)) - 1;
-    uint64_t aaAcc = 0, smAcc = 0;
-    uint64_t sm[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // sm[k]: the s-mer ending k codons back
-    int run = 0;
     uint64_t* kOut = keys + u * kGroupChunk;
     uint32_t* iOut = ids + u * kGroupChunk;
     const uint32_t id = idBase + r + 1;
@@ -415,35 +398,11 @@ __global__ void __launch_bounds__(256) k_extract_aa12(const uint8_t* __restrict_
     // SyncmerScanner.h:287-289), mate 2 after getMaxCoveredLength(len1) + 3 (KmerExtractor.cpp:341-345)
     uint32_t* pOut = pos ? pos + u * kGroupChunk : nullptr;
     const int posBase = (fwd ? s0 : e0 - 3 * kGroupK + 1) + (mate ? max_covered_length(m.len1) + 3 : 0);
-    for (int j = pFirst; j < pFirst + nWin + kGroupK - 1; j++) {
-        const int d = fwd ? 1 : -1;
-        const int c0 = fwd ? s0 + 3 * j : e0 - 3 * j;
-        const uint32_t x = sBase[seq[c0]], y = sBase[seq[c0 + d]], z = sBase[seq[c0 + 2 * d]];
-        const uint32_t cm = fwd ? 0u : 2u;  // complement of a valid code (iRCT)
-        const bool valid = (x | y | z) < 4u;
-        const int aaT = sAA[(((x ^ cm) << 4) | ((y ^ cm) << 2) | (z ^ cm)) & 63u];
-        const bool ok = valid && aaT >= 0;
-        run = ok ? run + 1 : 0;
-        aaAcc = ok ? (aaAcc << 5) | (uint64_t)aaT : aaAcc;
-        smAcc = ok ? ((smAcc << 5) | (uint64_t)aaT) & smMask : smAcc;
-#pragma unroll
-        for (int k = 7; k > 0; k--) sm[k] = sm[k - 1];
-        sm[0] = smAcc;
-        const int p = j - pFirst - (kGroupK - 1);
-        if (p < 0) continue;
-        bool emit = run >= kGroupK;
-        if (emit && syncmer) {
-            int bestK = -1;
-            uint64_t best = ~0ull;
-#pragma unroll
-            for (int k = 7; k >= 0; k--)  // from the oldest s-mer to the newest, strict <: the earliest minimum
-                if (k <= nSm - 1 && sm[k] < best) { best = sm[k]; bestK = k; }
-            emit = bestK == nSm - 1 || bestK == 0;
-        }
-        kOut[p] = emit ? (aaAcc & kAA12Mask) : kSentinel;
+    scan_aa12_chunk(seq, fwd, s0, e0, pFirst, nWin, syncmer, smerLen, sBase, sAA, [&](int p, bool keep, uint64_t value) {
+        kOut[p] = keep ? value : kSentinel;
         iOut[p] = id;
         if (pOut) pOut[p] = (uint32_t)(fwd ? posBase + 3 * (pFirst + p) : posBase - 3 * (pFirst + p));
-    }
+    });
     for (int p = max(nWin, 0); p < (int)kGroupChunk; p++) {
         kOut[p] = kSentinel;
         iOut[p] = id;

@@ -464,7 +464,8 @@ void launch_em_reclassify(const float* score, const uint32_t* spIdx, const int32
 // and the split table into out's host arrays, or with deviceOut the resident-form values + info
 // into out->dev_*. The split's sizeOfSplit is splitTotal / (splitNum - 1): kSplitByUnique takes the
 // unique count (writeTargetFilesAndSplits, IndexCreator.cpp:819), a merge passes its k-mer count
-// before merging (IndexCreator.h:343). scanTmp: scan_tmp_elems(kept + 2) u64, or null (allocated
+// before merging (IndexCreator.h:343). kmerFormat 3 and 5 (the common-k-mer DB, mtb_common.hip): the
+// AA part of the split rule is the whole value (IndexCreator.h:209-214). scanTmp: scan_tmp_elems(kept + 2) u64, or null (allocated
 // here). evDedupe (nullable): recorded after the dedupe + LCA. Returns MTB_OK or an error code
 // (set_error called); out's taxid_list is left to the caller.
 struct HostTaxonomy;
@@ -475,6 +476,11 @@ int encode_sorted_kmers(const uint64_t* keys, const uint64_t* pay, uint64_t kept
 // Items per tile of the two-way merge (mtb_merge.hip)
 constexpr uint32_t kMergeDbPer = 8;
 constexpr uint32_t kMergeDbTile = 256 * kMergeDbPer;
+// The two-way merge itself: sorted runs a and b in (value, payload) order into o (nA + nB pairs), equal
+// pairs taking a's first. part: (nA + nB + kMergeDbTile - 1) / kMergeDbTile + 1 u64 of scratch. The
+// caller keeps nA + nB below 2^31 tiles.
+void launch_merge_pairs(const uint64_t* aK, const uint64_t* aP, uint64_t nA, const uint64_t* bK, const uint64_t* bP,
+                        uint64_t nB, uint64_t* part, uint64_t* oK, uint64_t* oP, hipStream_t s);
 
 // ---- K0M: tantan low-complexity masking of the reads (mtb_mask.hip; --mask-residues 1) ----------
 constexpr int kTantanOffsets = 50;  // tantan's maxCycleLength (SeqIterator.cpp:163)

@@ -143,6 +143,14 @@ __global__ void __launch_bounds__(256) k_merge_tile(const uint64_t* __restrict__
     }
 }
 
+void launch_merge_pairs(const uint64_t* aK, const uint64_t* aP, uint64_t nA, const uint64_t* bK, const uint64_t* bP,
+                        uint64_t nB, uint64_t* part, uint64_t* oK, uint64_t* oP, hipStream_t s) {
+    const uint64_t nTiles = (nA + nB + kMergeDbTile - 1) / kMergeDbTile;
+    if (!nTiles) return;
+    k_merge_partition<<<stride_grid(nTiles + 1), 256, 0, s>>>(aK, aP, nA, bK, bP, nB, nTiles, part);
+    k_merge_tile<<<(unsigned)nTiles, 256, 0, s>>>(aK, aP, nA, bK, bP, nB, part, oK, oP);
+}
+
 namespace {
 
 struct DevMem {  // one device allocation, freed on every return
@@ -270,12 +278,8 @@ int merge_two(const Stream& a, const Stream& b, Stream& out, hipStream_t s) {
     // ties take the lower-numbered input first
     const Stream& x = a.first <= b.first ? a : b;
     const Stream& y = a.first <= b.first ? b : a;
-    k_merge_partition<<<stride_grid(nTiles + 1), 256, 0, s>>>(x.k->as<uint64_t>(), x.p->as<uint64_t>(), x.n,
-                                                              y.k->as<uint64_t>(), y.p->as<uint64_t>(), y.n, nTiles,
-                                                              part.as<uint64_t>());
-    k_merge_tile<<<(unsigned)nTiles, 256, 0, s>>>(x.k->as<uint64_t>(), x.p->as<uint64_t>(), x.n, y.k->as<uint64_t>(),
-                                                  y.p->as<uint64_t>(), y.n, part.as<uint64_t>(), out.k->as<uint64_t>(),
-                                                  out.p->as<uint64_t>());
+    launch_merge_pairs(x.k->as<uint64_t>(), x.p->as<uint64_t>(), x.n, y.k->as<uint64_t>(), y.p->as<uint64_t>(), y.n,
+                       part.as<uint64_t>(), out.k->as<uint64_t>(), out.p->as<uint64_t>(), s);
     HIP_M(hipGetLastError());
     HIP_M(hipStreamSynchronize(s));  // part and the inputs are freed by the caller
     return MTB_OK;

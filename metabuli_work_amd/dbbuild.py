@@ -128,6 +128,8 @@ def _lib_build():
     L = lib()
     L.mtb_build_db.argtypes = [ctypes.POINTER(MtbBuildInput), ctypes.POINTER(MtbDbHost), ctypes.POINTER(MtbParams),
                                ctypes.c_int, ctypes.POINTER(MtbDbBuilt)]
+    L.mtb_build_common_db.argtypes = [ctypes.POINTER(MtbBuildInput), ctypes.POINTER(MtbDbHost), ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, ctypes.POINTER(MtbDbBuilt)]
     L.mtb_free_built.argtypes = [ctypes.POINTER(MtbDbBuilt)]
     L.mtb_merge_db.argtypes = [ctypes.POINTER(MtbMergeInput), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
                                ctypes.POINTER(MtbDbHost), ctypes.POINTER(MtbParams), ctypes.c_int, ctypes.c_int,
@@ -245,6 +247,55 @@ def update_db(old_dir: str, gen, taxo, par: MtbParams, out_dir: str, device: int
     merged = merge_dbs([load_db_dir(old_dir, taxo), new], taxo, par, device, split_num)
     merged.write(out_dir, par)
     return merged
+
+
+def build_common_kmer_db(gen, taxo, out_dir: Optional[str], syncmer: int = 1, smer_len: int = 5, device: int = 0,
+                         split_num: int = 4096, device_seq=None) -> HostDb:
+    """Build the common-k-mer DB of read grouping on the GPU (mtb_build_common_db, csrc/mtb_common.hip;
+    the reference's create_common_kmer_list): the AA 12-mers (``syncmer=1``: the syncmers of ``smer_len``)
+    of all six frames of every genome of ``gen`` that genomes of two or more species hold, with the LCA
+    of those species as info. ``gen.seq`` / ``gen.off`` / ``gen.taxid`` are read (whole genomes, no gene
+    blocks); ``device_seq`` = (seq, off) torch tensors already in HBM. Writes diffIdx, info, split,
+    taxID_list, db.parameters (Kmer_format 3, or 5 with syncmers) and kmer_params to ``out_dir`` (None:
+    nothing is written) with the taxonomy as ``HostDb.write`` writes it (``taxo.write_dmp``: every taxonomy
+    this package holds is one in memory; there is no loader from a DB directory whose files could be
+    copied). ``grouping.group_reads(..., common_db=out_dir)`` takes the directory."""
+    hdb = HostDb(taxo)
+    inp = MtbBuildInput()
+    if device_seq is not None:
+        inp.seq, inp.off = device_seq[0].data_ptr(), device_seq[1].data_ptr()
+        inp.flags = MTB_INPUT_DEVICE
+    else:
+        seq, off = np.ascontiguousarray(gen.seq, np.uint8), np.ascontiguousarray(gen.off, np.uint64)
+        inp.seq, inp.off = seq.ctypes.data, off.ctypes.data
+        inp.flags = 0
+    taxid = np.ascontiguousarray(gen.taxid, np.int32)
+    inp.n_genomes = len(taxid)
+    inp.genome_taxid = taxid.ctypes.data
+    inp.n_blocks = 0
+    inp.split_num = split_num
+    out = MtbDbBuilt()
+    L = _lib_build()
+    tax_struct = hdb.c_struct()
+    check(L.mtb_build_common_db(ctypes.byref(inp), ctypes.byref(tax_struct), int(syncmer), int(smer_len), device,
+                                ctypes.byref(out)), "mtb_build_common_db")
+    _take_built(hdb, out, L)
+    if out_dir is not None:
+        par = MtbParams()
+        lib().mtb_default_params(ctypes.byref(par))
+        par.syncmer, par.smer_len, par.kmer_format = int(syncmer), int(smer_len), 5 if syncmer else 3
+        hdb.write(out_dir, par)
+        with open(os.path.join(out_dir, "kmer_params"), "w") as f:  # create_common_kmer_list.cpp:98-107
+            f.write(f"syncmer {int(syncmer)}\nsmer_len {int(smer_len)}\nkmer_format {5 if syncmer else 3}\n")
+    return hdb
+
+
+def common_last_ms():
+    """Phase times of this process's last common-k-mer build in ms: extraction, sort, reduce, fold,
+    encode + split, total."""
+    ms = (ctypes.c_float * 6)()
+    check(lib().mtb_common_last_ms(ms, 6), "mtb_common_last_ms")
+    return [float(x) for x in ms]
 
 
 def merge_last_ms():

@@ -243,7 +243,8 @@ def group_reads(query1, query2, out_dir, par: GroupParams = None, device: int = 
                 max_reads: int = 1 << 20, max_bases: int = 1 << 30, common_db=None):
     """groupGeneration over FASTA / FASTQ files (plain or gzip): batches streamed through mtb_reader_*,
     the graph and the phases on the device; writes out_dir/groupMap, groups and skipped_kmers
-    ("value \\t m" per skipped k-mer). common_db: a common-k-mer DB directory; every batch then goes
+    ("value \\t m" per skipped k-mer). common_db: a common-k-mer DB directory (the reference's create_common_kmer_list's, or
+    dbbuild.build_common_kmer_db's); every batch then goes
     through the common-k-mer filter and stats["filter"] holds its counts. Returns (groupMap, stats)."""
     import pathlib
 
