@@ -625,8 +625,8 @@ void mtb_group_default_params(mtb_group_params* par);
 /* A grouping run on one device: batches of reads in, the shared-k-mer graph and the groupMap out.
  * Everything stays resident in HBM (no kmer_delta_* / subGraph_* spill). With a common-k-mer set
  * attached (below) every batch goes through filterCommonKmers before it is stored; without one the
- * graph is over all extracted k-mers. Out of scope: masking, mergeGraph_one, GroupApplier, more than
- * one GPU. */
+ * graph is over all extracted k-mers. Out of scope: masking, mergeGraph_one, more than one GPU. The
+ * groupMap goes on to mtb_group_apply (below). */
 typedef struct mtb_grouper mtb_grouper;
 int mtb_group_open(const mtb_group_params* par, int device, mtb_grouper** out);
 void mtb_group_close(mtb_grouper* g);
@@ -711,6 +711,80 @@ void mtb_group_filter_constants(uint32_t out[4]);
 int mtb_group_make_groups(int device, const mtb_relation* edges, uint64_t n_edges, uint32_t n_reads,
                           uint64_t total_kmers, const mtb_group_params* par, uint32_t* phase_maps,
                           mtb_group_stats* stats);
+
+/* ---- group application (src/read-group/GroupApplier.cpp, workflow groupApplication) ----------------
+ * Every group gets one representative taxon, the weighted-majority label of its members'
+ * classifications, and the reads the classifier left unclassified or scored low take it.
+ * Votes (getRepLabel, GroupApplier.cpp:134-192): a member of a group (group ID != 0) votes iff its
+ * internal label is not 0 and, in weight modes 1 and 2, score >= min_vote_score (float compare); weight
+ * 1, score, or the float product score * score. The representative is weightedMajorityLCA(votes, 0.5);
+ * 0 or 1 (the root) = none. PARITY UNPINNED: weightedMajorityLCA is MMseqs2's, absent from the
+ * reference tree, restated from the published algorithm: a vote adds its weight to its node and every
+ * ancestor; a node is a candidate iff it is some vote's label or the LCA of two labels; total = the sum
+ * of all weights (0: no representative); of the candidates with weight / total >= 0.5 the one of the
+ * smallest lineage rank wins (the rank index of the first ranked node from the candidate towards the
+ * root, the root never looked at; none: larger than every rank), then the largest share, then the
+ * smallest internal taxID. Sums are in double, in a fixed order where the reference's follow its
+ * unordered_set: per (group, label) slices of out[0] (mtb_group_apply_constants) consecutive members in
+ * read order, each from 0.0, the slice sums added in slice order; a candidate's weight and the total
+ * over the group's labels ascending by taxID. A result differs from a given reference build only where a
+ * share lies within rounding of 0.5 or of another candidate's.
+ * Per read (applyRepLabel, GroupApplier.cpp:194-237): with a representative, mode 0 takes it; modes 1
+ * and 2 take it iff the read's label is 0 or its score < min_vote_score; every other read keeps its
+ * label (classified iff it is not 0). A merged taxID votes as the node it was merged into. */
+typedef struct mtb_group_apply_params { /* setGroupApplicationDefaults, groupApplication.cpp:7-15 */
+    int32_t weight_mode;          /* --weight-mode: 0 uniform, 1 score, 2 score^2 (1)                */
+    float min_vote_score;         /* --min-vote-scr (0.15)                                          */
+    int32_t reserved[2];
+} mtb_group_apply_params;
+/* labels: distinct (group, label) pairs that vote. ms: device time per stage: [0] keys and sort,
+ * [1] per-label sums, [2] per-group choice, [3] apply. */
+typedef struct mtb_group_apply_stats {
+    uint64_t reads, voting_reads, labels, groups, groups_with_rep, applied;
+    float ms[4];
+} mtb_group_apply_stats;
+void mtb_group_apply_default_params(mtb_group_apply_params* par);
+/* group_map: n_reads + 1 entries in mtb_group_finish's layout (entry 0 unused); tax_ids / scores: per
+ * read, internal taxIDs of `taxonomy` (only its taxonomy fields are read) and the classifier's scores
+ * (not read in mode 0, may be NULL). flags: MTB_INPUT_DEVICE (the per-read arrays and rep_group /
+ * rep_tax are device pointers, the outputs are written on the device) or 0. rep_group / rep_tax: every
+ * group ID of group_map ascending and its representative (0: none); *n_groups: their capacity in, the
+ * groups out; MTB_RETRY (n_groups set) when it is too small. out_tax / out_classified / out_applied
+ * (n_reads each): the read's label, is_classified, and 1 where it took the representative.
+ * MTB_ERR_ARG: weight_mode outside 0..2, a non-zero label the taxonomy does not hold (the first such
+ * read is named), a group ID of 2^32 - 1, 2^32 - 1 reads or more (host arrays: before any device call);
+ * MTB_ERR_OOM (the bytes needed in mtb_last_error) when the call does not fit the device. */
+int mtb_group_apply(int device, const mtb_db_host* taxonomy, const mtb_group_apply_params* par,
+                    const uint32_t* group_map, const int32_t* tax_ids, const float* scores, uint64_t n_reads,
+                    uint32_t flags, uint32_t* rep_group, int32_t* rep_tax, uint64_t* n_groups, int32_t* out_tax,
+                    uint8_t* out_classified, uint8_t* out_applied, mtb_group_apply_stats* stats);
+/* Staged: the per-label sums of the same call on host arrays: keys[i] = group << 32 | label ascending,
+ * sums[i] = W(group, label); an entry of label 0 stands for the group's members without a vote (sum 0).
+ * MTB_RETRY (n set) when cap is too small. */
+int mtb_group_apply_label_sums(int device, const mtb_db_host* taxonomy, const mtb_group_apply_params* par,
+                               const uint32_t* group_map, const int32_t* tax_ids, const float* scores,
+                               uint64_t n_reads, uint64_t* keys, double* sums, uint64_t cap, uint64_t* n);
+/* The lineage rank of every node of `taxonomy` (n_nodes entries, node order), as uploaded. Host only. */
+int mtb_group_apply_lineage_ranks(const mtb_db_host* taxonomy, int32_t* out);
+/* out[0] members per slice of a label's sum, out[1] the most labels of a group a thread chooses for,
+ * out[2] the most a wave chooses for with the labels in LDS (a workgroup reads larger groups from HBM),
+ * out[3] 0. */
+void mtb_group_apply_constants(uint32_t out[4]);
+/* GroupApplier::startGroupApplication over files: classifications_tsv (lines starting with '#' and empty
+ * lines skipped; columns 1-based, the reference's defaults 3, 5, 2; at most 20 columns are split; with
+ * weight_mode 0 or score_col < 1 every score is 1), groupmap_path ("readId \t groupId" per read),
+ * taxonomy_dir (nodes.dmp, names.dmp, merged.dmp; internal taxIDs as the reference numbers them, from 1
+ * in order of first appearance in nodes.dmp, which must begin with the root: MTB_ERR_UNSUPPORTED
+ * otherwise). groups_path may be NULL; given, it must hold groupMap's membership (MTB_ERR_ARG). Writes
+ * out_dir/groupRep ("groupId \t original taxID", 0 = none, groups ascending where the reference's
+ * follow its hash order) and out_dir/updated_classifications.tsv as Reporter::writeReadClassification
+ * (queryList, groupIdList) writes it (query_length 0, no taxID:match_count, no lineage).
+ * MTB_ERR_ARG, before any device call: weight_mode outside 0..2, groupMap and the TSV differ in reads,
+ * a column outside a row or without a number, a non-zero label the taxonomy does not hold (the first
+ * such read is named), a group ID of 2^32 - 1 or more. */
+int mtb_group_apply_files(const char* groups_path, const char* groupmap_path, const char* taxonomy_dir,
+                          const char* classifications_tsv, const char* out_dir, const mtb_group_apply_params* par,
+                          int taxid_col, int score_col, int read_id_col, int device, mtb_group_apply_stats* stats);
 
 #ifdef __cplusplus
 }

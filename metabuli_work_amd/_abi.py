@@ -128,7 +128,8 @@ class MtbEmStats(ctypes.Structure):
                 ("delta", ctypes.c_double)]
 
 
-# read grouping (include/mtb_gpu.h: mtb_group_params, mtb_relation, mtb_group_stats, mtb_group_filter_stats)
+# read grouping (include/mtb_gpu.h: mtb_group_params, mtb_relation, mtb_group_stats, mtb_group_filter_stats,
+# mtb_group_apply_params, mtb_group_apply_stats)
 class MtbGroupParams(ctypes.Structure):
     _fields_ = [("seq_mode", ctypes.c_int32), ("syncmer", ctypes.c_int32), ("smer_len", ctypes.c_int32),
                 ("max_kmer_reads", ctypes.c_int32), ("max_kmer_quantile", ctypes.c_float),
@@ -150,6 +151,16 @@ class MtbGroupFilterStats(ctypes.Structure):
     _fields_ = [("extracted", ctypes.c_uint64), ("db_values", ctypes.c_uint64), ("hit", ctypes.c_uint64),
                 ("removed", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("params_checked", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("ms", ctypes.c_float * 4)]
+
+
+class MtbGroupApplyParams(ctypes.Structure):
+    _fields_ = [("weight_mode", ctypes.c_int32), ("min_vote_score", ctypes.c_float), ("reserved", ctypes.c_int32 * 2)]
+
+
+class MtbGroupApplyStats(ctypes.Structure):
+    _fields_ = [("reads", ctypes.c_uint64), ("voting_reads", ctypes.c_uint64), ("labels", ctypes.c_uint64),
+                ("groups", ctypes.c_uint64), ("groups_with_rep", ctypes.c_uint64), ("applied", ctypes.c_uint64),
+                ("ms", ctypes.c_float * 4)]
 
 
 RELATION_DTYPE = np.dtype([("id1", "<u4"), ("id2", "<u4"), ("weight", "<u2"), ("pad", "<u2")])

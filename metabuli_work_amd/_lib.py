@@ -7,8 +7,8 @@ entry point raises. Build it with `python -c "import __graft_entry__ as g; g.bui
 import ctypes
 import pathlib
 
-from ._abi import (MtbClassifyOpts, MtbClassifyStats, MtbDbHost, MtbDbResident, MtbEmStats, MtbGroupFilterStats,
-                   MtbGroupParams, MtbGroupStats, MtbParams, MtbReadBatch)
+from ._abi import (MtbClassifyOpts, MtbClassifyStats, MtbDbHost, MtbDbResident, MtbEmStats, MtbGroupApplyParams,
+                   MtbGroupApplyStats, MtbGroupFilterStats, MtbGroupParams, MtbGroupStats, MtbParams, MtbReadBatch)
 
 _HERE = pathlib.Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libmtbgpu.so"
@@ -32,6 +32,8 @@ EXPORTED = [
     "mtb_group_set_common_db", "mtb_group_set_common_kmers", "mtb_group_get_filter_stats", "mtb_group_get_kmer_pos",
     "mtb_group_filter_common", "mtb_group_filter_constants",
     "mtb_build_common_db", "mtb_common_last_ms", "mtb_common_unit_windows",
+    "mtb_group_apply_default_params", "mtb_group_apply", "mtb_group_apply_label_sums", "mtb_group_apply_lineage_ranks",
+    "mtb_group_apply_constants", "mtb_group_apply_files",
 ]
 
 
@@ -135,6 +137,16 @@ def lib() -> ctypes.CDLL:
     L.mtb_group_filter_common.argtypes = [i32, vp, u64, vp, vp, vp, u64, vp, vp]
     L.mtb_group_filter_constants.argtypes = [P(u32 * 4)]
     L.mtb_group_filter_constants.restype = None
+    L.mtb_group_apply_default_params.argtypes = [P(MtbGroupApplyParams)]
+    L.mtb_group_apply_default_params.restype = None
+    L.mtb_group_apply.argtypes = [i32, P(MtbDbHost), P(MtbGroupApplyParams), vp, vp, vp, u64, u32, vp, vp, P(u64), vp, vp,
+                                  vp, P(MtbGroupApplyStats)]
+    L.mtb_group_apply_label_sums.argtypes = [i32, P(MtbDbHost), P(MtbGroupApplyParams), vp, vp, vp, u64, vp, vp, u64, P(u64)]
+    L.mtb_group_apply_lineage_ranks.argtypes = [P(MtbDbHost), vp]
+    L.mtb_group_apply_constants.argtypes = [P(u32 * 4)]
+    L.mtb_group_apply_constants.restype = None
+    L.mtb_group_apply_files.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                        P(MtbGroupApplyParams), i32, i32, i32, i32, P(MtbGroupApplyStats)]
     L.mtb_debug_tables.argtypes = [vp, vp, vp]
     L.mtb_debug_tables.restype = None
     _LIB = L

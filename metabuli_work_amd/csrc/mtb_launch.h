@@ -36,6 +36,7 @@ struct TaxDevice {
     const uint8_t* flags;
     const int32_t* spParent;
     int32_t maxTax;
+    const int32_t* lineageRank = nullptr;  // node -> lineage rank (group application, mtb_apply.hip); else unset
 };
 
 struct AssignArgs {

@@ -1,6 +1,10 @@
 """Read grouping on the GPU (the reference fork's groupGeneration workflow): the binding of the
 mtb_group_* section of include/mtb_gpu.h.
 
+apply_groups_arrays / apply_groups are the groupApplication workflow (GroupApplier): one representative
+taxon per group, the weighted-majority label of its members, applied to the reads the classifier left
+unclassified or scored low.
+
 make_groups runs the three grouping phases (makeGroups, mergeBySupport at its defaults,
 makeGroupsPhase2) on an edge list and returns the groupMap after each phase. filter_common runs the
 common-k-mer filter's kernels (filterCommonKmers) on instance arrays.
@@ -10,7 +14,8 @@ import dataclasses
 
 import numpy as np
 
-from ._abi import RELATION_DTYPE, MtbGroupFilterStats, MtbGroupParams, MtbGroupStats
+from ._abi import (MTB_INPUT_DEVICE, MTB_RETRY, RELATION_DTYPE, MtbGroupApplyParams, MtbGroupApplyStats,
+                   MtbGroupFilterStats, MtbGroupParams, MtbGroupStats)
 from ._lib import check, lib
 
 
@@ -281,3 +286,153 @@ def group_reads(query1, query2, out_dir, par: GroupParams = None, device: int = 
     with open(pathlib.Path(out_dir) / "skipped_kmers", "wb") as f:
         f.write("".join(f"{v}\t{m}\n" for v, m in zip(sv.tolist(), sm.tolist())).encode())
     return gm, st
+
+
+# ---- group application (mtb_group_apply*, the reference's GroupApplier) -----------------------------
+@dataclasses.dataclass
+class ApplyParams:
+    """setGroupApplicationDefaults (groupApplication.cpp:7-15): weight_mode 0 uniform, 1 score,
+    2 score^2; a member votes with score >= min_vote_score (modes 1 and 2)."""
+    weight_mode: int = 1
+    min_vote_score: float = 0.15
+
+    def to_c(self) -> MtbGroupApplyParams:
+        return MtbGroupApplyParams(weight_mode=self.weight_mode, min_vote_score=self.min_vote_score)
+
+    @classmethod
+    def defaults(cls) -> "ApplyParams":
+        """The library's own defaults (mtb_group_apply_default_params)."""
+        p = MtbGroupApplyParams()
+        lib().mtb_group_apply_default_params(ctypes.byref(p))
+        return cls(weight_mode=p.weight_mode, min_vote_score=p.min_vote_score)
+
+
+def apply_constants() -> dict:
+    """The sizes at which the applier's kernels change path (mtb_group_apply_constants)."""
+    c = (ctypes.c_uint32 * 4)()
+    lib().mtb_group_apply_constants(ctypes.byref(c))
+    return {"slice": c[0], "thread_labels": c[1], "wave_labels": c[2]}
+
+
+def _taxonomy_struct(taxo):
+    from .dbbuild import HostDb
+
+    h = HostDb(taxo)
+    return h, h.c_struct()
+
+
+def lineage_ranks(taxo) -> np.ndarray:
+    """The lineage rank of every node of taxo (node order), as the applier uploads it."""
+    keep, h = _taxonomy_struct(taxo)
+    out = np.zeros(len(taxo.taxid), np.int32)
+    check(lib().mtb_group_apply_lineage_ranks(ctypes.byref(h), out.ctypes.data), "mtb_group_apply_lineage_ranks")
+    return out
+
+
+def apply_groups_arrays(group_map, tax_ids, scores, taxo, par: ApplyParams = None, device: int = 0):
+    """One representative taxon per group and the per-read labels after applying it (mtb_group_apply).
+
+    group_map: reads + 1 uint32 entries as ReadGrouper.finish() returns them (entry 0 unused); tax_ids:
+    int32 internal taxIDs of taxo (a synth.Taxonomy: taxid, parent, rank, name), 0 = unclassified;
+    scores: float32 (None in weight mode 0). numpy arrays, or torch tensors on the device: then nothing
+    is copied to the host and the results are device tensors too (import torch before the library is first
+    used). Returns (rep_groups, rep_tax, out_tax,
+    out_classified, applied, stats): every group ID ascending with its representative (0 = none), and
+    per read its label, is_classified and whether it took the representative.
+
+        gm, _ = grouper.finish()                          # ReadGrouper
+        res = classifier.classify(reads)                  # RESULT_DTYPE records
+        groups, reps, tax, cls, applied, st = apply_groups_arrays(
+            gm, res["classification"], res["score"], taxo, ApplyParams.defaults())
+    """
+    par = par or ApplyParams.defaults()
+    keep, h = _taxonomy_struct(taxo)
+    cp = par.to_c()
+    st = MtbGroupApplyStats()
+    on_device = hasattr(group_map, "data_ptr")
+    if on_device:
+        import torch
+
+        dev = group_map.device
+        gm = group_map.to(torch.int32) if group_map.dtype not in (torch.int32, torch.uint32) else group_map
+        gm = gm.contiguous()
+        tx = tax_ids.to(device=dev, dtype=torch.int32).contiguous()
+        sc = None if scores is None else scores.to(device=dev, dtype=torch.float32).contiguous()
+        n = gm.numel() - 1
+        if tx.numel() != n or (sc is not None and sc.numel() != n):
+            raise ValueError("group_map holds reads + 1 entries; tax_ids and scores one per read")
+        out_tax = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        out_cls = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        out_app = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        cap = max(int(n), 1)
+        rg = torch.zeros(cap, dtype=torch.int32, device=dev)
+        rt = torch.zeros(cap, dtype=torch.int32, device=dev)
+        ng = ctypes.c_uint64(cap)
+        torch.cuda.synchronize(dev)
+        check(lib().mtb_group_apply(device, ctypes.byref(h), ctypes.byref(cp), gm.data_ptr(), tx.data_ptr(),
+                                    sc.data_ptr() if sc is not None else None, n, MTB_INPUT_DEVICE, rg.data_ptr(),
+                                    rt.data_ptr(), ctypes.byref(ng), out_tax.data_ptr(), out_cls.data_ptr(),
+                                    out_app.data_ptr(), ctypes.byref(st)), "mtb_group_apply")
+        g = ng.value
+        return rg[:g], rt[:g], out_tax[:n], out_cls[:n].bool(), out_app[:n].bool(), stats_dict(st)
+    gm = np.ascontiguousarray(group_map, np.uint32)
+    tx = np.ascontiguousarray(tax_ids, np.int32)
+    sc = None if scores is None else np.ascontiguousarray(scores, np.float32)
+    n = len(gm) - 1
+    if n < 0 or len(tx) != n or (sc is not None and len(sc) != n):
+        raise ValueError("group_map holds reads + 1 entries; tax_ids and scores one per read")
+    out_tax, out_cls, out_app = np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    cap = max(len(np.unique(gm[1:][gm[1:] != 0])), 1)
+    rg, rt = np.zeros(cap, np.uint32), np.zeros(cap, np.int32)
+    ng = ctypes.c_uint64(cap)
+    p = lambda a: a.ctypes.data if a is not None and len(a) else None
+    check(lib().mtb_group_apply(device, ctypes.byref(h), ctypes.byref(cp), gm.ctypes.data, p(tx), p(sc), n, 0,
+                                rg.ctypes.data, rt.ctypes.data, ctypes.byref(ng), p(out_tax), p(out_cls), p(out_app),
+                                ctypes.byref(st)), "mtb_group_apply")
+    g = ng.value
+    return rg[:g], rt[:g], out_tax, out_cls.astype(bool), out_app.astype(bool), stats_dict(st)
+
+
+def apply_label_sums(group_map, tax_ids, scores, taxo, par: ApplyParams = None, device: int = 0):
+    """Staged: the per-label sums of apply_groups_arrays on host arrays: (groups, labels, sums) of every
+    voting (group, label) pair, ascending (mtb_group_apply_label_sums)."""
+    par = par or ApplyParams.defaults()
+    keep, h = _taxonomy_struct(taxo)
+    cp = par.to_c()
+    gm = np.ascontiguousarray(group_map, np.uint32)
+    tx = np.ascontiguousarray(tax_ids, np.int32)
+    sc = None if scores is None else np.ascontiguousarray(scores, np.float32)
+    n = len(gm) - 1
+    cap = max(n, 1)
+    keys, sums = np.zeros(cap, np.uint64), np.zeros(cap, np.float64)
+    k = ctypes.c_uint64()
+    p = lambda a: a.ctypes.data if a is not None and len(a) else None
+    check(lib().mtb_group_apply_label_sums(device, ctypes.byref(h), ctypes.byref(cp), gm.ctypes.data, p(tx), p(sc), n,
+                                           keys.ctypes.data, sums.ctypes.data, cap, ctypes.byref(k)),
+          "mtb_group_apply_label_sums")
+    keys, sums = keys[:k.value], sums[:k.value]
+    vote = (keys & np.uint64(0xFFFFFFFF)) != 0
+    return ((keys[vote] >> np.uint64(32)).astype(np.uint32), (keys[vote] & np.uint64(0xFFFFFFFF)).astype(np.int32),
+            sums[vote])
+
+
+def apply_groups(group_dir, taxonomy_dir, classifications_tsv, out_dir, par: ApplyParams = None, taxid_col: int = 3,
+                 score_col: int = 5, read_id_col: int = 2, device: int = 0, check_groups: bool = True) -> dict:
+    """groupApplication over files (mtb_group_apply_files): group_dir holds groupMap and groups as
+    group_reads wrote them, taxonomy_dir the dmp files, classifications_tsv the classifier's per-read
+    TSV (columns 1-based). Writes out_dir/groupRep (groups ascending) and
+    out_dir/updated_classifications.tsv; returns the stats. check_groups: also hold group_dir/groups
+    against groupMap."""
+    import pathlib
+
+    par = par or ApplyParams.defaults()
+    gd = pathlib.Path(group_dir)
+    pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
+    cp = par.to_c()
+    st = MtbGroupApplyStats()
+    groups = str(gd / "groups").encode() if check_groups and (gd / "groups").exists() else None
+    check(lib().mtb_group_apply_files(groups, str(gd / "groupMap").encode(), str(taxonomy_dir).encode(),
+                                      str(classifications_tsv).encode(), str(out_dir).encode(), ctypes.byref(cp),
+                                      taxid_col, score_col, read_id_col, device, ctypes.byref(st)),
+          "mtb_group_apply_files")
+    return stats_dict(st)
